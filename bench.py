@@ -8,7 +8,14 @@ Inputs are resident in HBM before timing.  Multi-GPU: one process per GPU
 (weak scaling, no collective on the data path); the timed region is
 bracketed by barrier + synchronize and the max over ranks is reported.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--records N]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--records N] [--dump-outputs DIR] [--full]
+
+Such a run sets up, warms up, times K steps and prints one JSON line; the
+legs beside the headline (checks of what was timed against the reference,
+other sizes, cold caches, host-inclusive rates, the CPU baseline, the N>1
+gather) run only with --full.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts
 the N rank processes itself (torch.distributed.run as a child process,
@@ -52,6 +59,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--records", "--n", dest="n", type=int, default=None,
                     help="records per GPU (default 1M at N=1, 2M at N>1: BASELINE.json configs 2 and 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every leg beside the headline (round trip and "
+                         "reference hash of what was timed, 16M and shard legs, cold caches, plain stream, "
+                         "host-inclusive rates, CPU baseline, --msgs/--rpc, the N>1 gather); the --no-* "
+                         "options below drop single legs of it.  Without it a run only sets up, warms up, "
+                         "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (the XDR stream, the "
+                         "decoded records; var schemas: the record index and the decoded heap too) as "
+                         "DIR/<name>.npy (float32/float64; a fixed seeded sample of arrays past the size cap)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large", action="store_true",
                     help="skip the 16M-record fixed-path leg (large_batch_16m)")
@@ -88,7 +105,13 @@ def parse():
     ap.add_argument("--plan-opt", action="append", default=[], metavar="NAME=V",
                     help="a plan option (xdrpp_amd._abi.PLAN_OPTIONS) for A/B runs, e.g. enc_stream=0; "
                          "echoed in config.plan_options")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    asked = [o for o in ("msgs", "rpc", "cold", "host_inclusive") if getattr(args, o)]
+    if asked and not args.full:
+        ap.error("--" + asked[0].replace("_", "-") + " is a leg beside the headline: give --full with it")
+    return args
 
 
 def _free_port() -> int:
@@ -724,21 +747,25 @@ def rpc_leg(dev, n=1 << 20, reps=20):
     return res
 
 
-def setup(schema, n, dev, rank, world, opts=None):
-    """Plan, resident inputs and preallocated outputs for one rank."""
+def setup(schema, n, dev, rank, world, opts=None, zero=False):
+    """Plan, resident inputs and preallocated outputs for one rank (`zero`:
+    outputs start as zeros, so that bytes no kernel writes -- padding of the
+    native records, the unused end of the decoded heap -- are the same from
+    run to run when the outputs are dumped)."""
     plan = M.Plan(S.ALL[schema], opts or None)
     mar = M.Marshaler(plan, dev)
     nat_np, heap_np = SH.shard_inputs(schema, n, rank, world)
     nat = torch.from_numpy(nat_np).to(dev)
     heap = torch.from_numpy(heap_np).to(dev) if heap_np.size else None
-    back = torch.empty(n * plan.stride, dtype=torch.uint8, device=dev)
+    alloc = torch.zeros if zero else torch.empty
+    back = alloc(n * plan.stride, dtype=torch.uint8, device=dev)
     if plan.is_fixed:
-        xdr = torch.empty(n * plan.fixed_size, dtype=torch.uint8, device=dev)
+        xdr = alloc(n * plan.fixed_size, dtype=torch.uint8, device=dev)
         return plan, mar, nat, heap, xdr, back, None, None
     total = int(mar.serial_sizes(nat, n, heap=heap).to(torch.int64).sum().item())
-    xdr = torch.empty(total, dtype=torch.uint8, device=dev)
-    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    heap_out = torch.empty(plan.decode_heap_bytes(total), dtype=torch.uint8, device=dev)
+    xdr = alloc(total, dtype=torch.uint8, device=dev)
+    offsets = alloc(n + 1, dtype=torch.int64, device=dev)
+    heap_out = alloc(plan.decode_heap_bytes(total), dtype=torch.uint8, device=dev)
     return plan, mar, nat, heap, xdr, back, offsets, heap_out
 
 
@@ -778,7 +805,8 @@ class GpuEngine:
         self.dev = torch.device("cuda", local)
         self.schema, self.n = args.schema, n
         (self.plan, self.mar, self.nat, self.heap, self.xdr, self.back, self.offsets,
-         self.heap_out) = setup(args.schema, n, self.dev, rank, world, plan_opts(args))
+         self.heap_out) = setup(args.schema, n, self.dev, rank, world, plan_opts(args),
+                                zero=bool(args.dump_outputs))
         self.enc_stream = plan_opts(args).get("enc_stream", -1)
         self.size_linear = plan_opts(args).get("size_linear", -1)
         self.fixed_path = plan_opts(args).get("fixed_path", 0)
@@ -896,6 +924,51 @@ class GpuEngine:
         """The rank's encoded stream and record index (for the gather)."""
         return self.xdr, self.offsets
 
+    def outputs(self) -> dict:
+        """What a caller of the step receives: the encoded stream and the
+        decoded native records; var schemas also the record index and the
+        decoded heap."""
+        out = {"xdr": self.xdr, "decoded_native": self.back}
+        if self.offsets is not None:
+            out["offsets"] = self.offsets
+            out["decoded_heap"] = self.heap_out
+        return out
+
+
+DUMP_CAP_BYTES = 60 * 1000 * 1000  # all dumped arrays together (float32 / float64 bytes)
+DUMP_BLOCK = 4096  # elements per sampled block
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_sample(t: torch.Tensor, budget: int, seed: int) -> np.ndarray:
+    """`t` flat as float32 (bytes; exact) or float64 (the int64 record
+    index; exact below 2**53), whole when it fits `budget` bytes, else a
+    sample fixed by `seed` and the length alone: the first and the last
+    block of DUMP_BLOCK elements and, between them, blocks drawn without
+    replacement, in order.  The sample is gathered where the tensor lives."""
+    t = t.reshape(-1)
+    ftype = torch.float32 if t.element_size() == 1 else torch.float64
+    fsize = 4 if ftype == torch.float32 else 8
+    if t.numel() * fsize > budget:
+        nblk = (t.numel() + DUMP_BLOCK - 1) // DUMP_BLOCK
+        k = max(2, budget // (fsize * DUMP_BLOCK))
+        rng = np.random.default_rng(seed)
+        mid = np.sort(rng.choice(np.arange(1, nblk - 1), size=k - 2, replace=False))
+        blocks = np.concatenate([[0], mid, [nblk - 1]]).astype(np.int64)
+        idx = (blocks[:, None] * DUMP_BLOCK + np.arange(DUMP_BLOCK, dtype=np.int64)[None, :]).reshape(-1)
+        idx = idx[idx < t.numel()]
+        t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+    return t.to(ftype).cpu().numpy()
+
+
+def dump_outputs(outs: dict, path: str, suffix: str = "") -> None:
+    """--dump-outputs: every output array as path/<name><suffix>.npy, each
+    within an equal share of DUMP_CAP_BYTES."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_CAP_BYTES // max(1, len(outs))
+    for i, (name, t) in enumerate(sorted(outs.items())):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), dump_sample(t, budget, DUMP_SEED + i))
+
 
 def load_engine(path: str):
     """--engine FILE: a module defining Engine (the tests' CPU stand-in)."""
@@ -1009,6 +1082,7 @@ def report(args, engine, world, rows, X, kern, alg_bytes, launches, enc_ms, dec_
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -1028,7 +1102,7 @@ def report(args, engine, world, rows, X, kern, alg_bytes, launches, enc_ms, dec_
                      "alg_bytes_per_launch": alg_bytes,
                      "timed_launches": len(launches),
                      "protocol": f"HIP events on the launch stream around both kernels of every {E}th timed step"},
-        "round_trip_ok": bool(rows[:, 5].all()),
+        "round_trip_ok": bool(rows[:, 5].all()) if args.full else None,  # checked with --full only
         "bit_exact_vs_reference": bit_exact,
     }
     if world > 1:
@@ -1052,14 +1126,16 @@ def main():
     engine = Engine(args, n, rank, world, local)
     engine.dist = dist
     elapsed, enc_ms, dec_ms = measure(engine, args)
+    if args.dump_outputs:
+        dump_outputs(engine.outputs(), args.dump_outputs, "" if world == 1 else f".rank{rank}")
 
-    # correctness of what was timed; on the 1-GPU headline config the stream
-    # also hashes to the reference's output
-    ok_rt = engine.round_trip_ok()
+    # --full: correctness of what was timed; on the 1-GPU headline config the
+    # stream also hashes to the reference's output
+    ok_rt = engine.round_trip_ok() if args.full else True
     xdr, _ = engine.shard()
     X = xdr.numel()
     man = os.path.join(ROOT, "tests", "golden", "manifest.json")
-    hashes = json.load(open(man))["hashes"] if os.path.exists(man) else {}
+    hashes = json.load(open(man))["hashes"] if args.full and os.path.exists(man) else {}
     bit_exact = None
     if world == 1 and f"{args.schema}_{n}" in hashes:
         bit_exact = hashlib.sha256(xdr.cpu().numpy().tobytes()).hexdigest() == hashes[f"{args.schema}_{n}"]["xdr"]
@@ -1070,7 +1146,7 @@ def main():
                                    float(ok_rt)], engine.dev)
     X_all = int(rows[:, 3].sum())
     gather = None
-    if dist is not None and not args.no_gather:
+    if dist is not None and args.full and not args.no_gather:
         gather = gather_leg(engine, dist, rank, world, X_all, X, rows, hashes, f"{args.schema}_mgpu_{n * world}")
         if gather is not None and "bit_exact_vs_reference" in gather:
             bit_exact = gather["bit_exact_vs_reference"]
@@ -1079,7 +1155,7 @@ def main():
             dist.destroy_process_group()
         return
     line = report(args, engine, world, rows, X, kern, alg_bytes, launches, enc_ms, dec_ms, bit_exact, gather)
-    if isinstance(engine, GpuEngine) and world == 1:
+    if args.full and isinstance(engine, GpuEngine) and world == 1:
         extra_legs(args, engine, line, alg_bytes)
     print(json.dumps(line), flush=True)
     if dist is not None:

@@ -71,3 +71,12 @@ class Engine:
     def shard(self):
         offs = torch.from_numpy(self.offs.view(np.int64).copy()) if self.cp.is_var else None
         return torch.from_numpy(np.ascontiguousarray(self.x)), offs
+
+    def outputs(self) -> dict:
+        xdr, offs = self.shard()
+        nat2, heap2 = self.back
+        out = {"xdr": xdr, "decoded_native": torch.from_numpy(np.ascontiguousarray(nat2).view(np.uint8))}
+        if offs is not None:
+            out["offsets"] = offs
+            out["decoded_heap"] = torch.from_numpy(np.ascontiguousarray(heap2).view(np.uint8))
+        return out

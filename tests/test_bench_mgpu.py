@@ -32,7 +32,7 @@ N = 700
 @pytest.mark.parametrize("schema", ["rec128", "recvar"])
 def test_bench_two_ranks(schema):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", str(N), "--steps", "3",
-           "--warmup", "1", "--event-every", "1", "--schema", schema,
+           "--warmup", "1", "--event-every", "1", "--schema", schema, "--full",
            "--engine", os.path.join(ROOT, "tests", "bench_cpu_engine.py")]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)

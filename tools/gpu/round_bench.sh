@@ -12,8 +12,8 @@ for s in rec128 numerics recvar rpc vecrec; do
   extra=""
   [ "$s" = recvar ] && extra="--msgs"
   [ "$s" = rpc ] && extra="--msgs --rpc"
-  timeout -k 10 300 python3 -u bench.py --schema "$s" --no-cpu-baseline --no-large $extra > "$O/bench_$s.log" 2>&1 || { rc=$?; break; }
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$s" -o k --output-format csv -- python3 bench.py --schema "$s" --no-cpu-baseline --no-large --steps 20 --warmup 5 > "$O/prof_$s.log" 2>&1 || { rc=$?; break; }
+  timeout -k 10 300 python3 -u bench.py --full --schema "$s" --no-cpu-baseline --no-large $extra > "$O/bench_$s.log" 2>&1 || { rc=$?; break; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$s" -o k --output-format csv -- python3 bench.py --full --schema "$s" --no-cpu-baseline --no-large --steps 20 --warmup 5 > "$O/prof_$s.log" 2>&1 || { rc=$?; break; }
   tail -1 "$O/bench_$s.log" | cut -c1-400
 done
 exit $rc

@@ -14,13 +14,13 @@ if [ -z "$NO_TESTS" ]; then
   tail -1 "$O/pytest_gpu.log"
   timeout -k 10 300 python3 -u -c 'import __graft_entry__ as g; g.smoke()' > "$O/smoke.log" 2>&1 || exit 1
 fi
-timeout -k 10 400 python3 -u bench.py > "$O/bench_rec128.log" 2>&1 || exit 1
+timeout -k 10 400 python3 -u bench.py --full > "$O/bench_rec128.log" 2>&1 || exit 1
 echo "[bench] rec128 done $(date +%T)"
 for s in numerics recvar rpc vecrec containertest rp_list; do
   extra=""
   [ "$s" = recvar ] && extra="$extra --msgs"
   [ "$s" = rpc ] && extra="$extra --msgs --rpc"
-  timeout -k 10 300 python3 -u bench.py --schema "$s" $extra > "$O/bench_$s.log" 2>&1 || exit 1
+  timeout -k 10 300 python3 -u bench.py --full --schema "$s" $extra > "$O/bench_$s.log" 2>&1 || exit 1
   echo "[bench] $s done $(date +%T)"
 done
 B="bench.py --no-cpu-baseline --no-large --no-cold --no-host-inclusive --no-plain --no-shard --steps 10 --warmup 3"
