@@ -561,10 +561,12 @@ size_t xdrg_index_workspace_size(uint64_t len, uint32_t max_msg_len);
 /*
  * Record index of n records of `plan` concatenated in one stream, the
  * input of xdr_from_opaque(bytes, r0, ..., rn-1) (xdrpp/marshal.h:299-306),
- * computed on the device.  First a speculative walk: each 16 KiB segment
- * of the stream guesses where the chain of records enters it, walks the
- * chain (lengths, counts and discriminants only) and every guess is
- * checked against the previous segment's exit; when all hold and the chain
+ * computed on the device.  First a speculative walk (streams of at least
+ * 27776 bytes, four segments): each 6944-byte segment of the stream
+ * guesses where the chain of records enters it, walks the chain (lengths,
+ * counts and discriminants only) and every guess is checked against the
+ * previous segment's exit; a few segments whose guess missed are walked
+ * again from the true entry; when all hold and the chain
  * ends at len with exactly n records, that is the index.  Otherwise
  * (damaged streams, trailing or missing records, long records, or a guess
  * that missed: XDRG_OPT_INDEX_FAST = 0 forces this) every word position is
@@ -595,10 +597,17 @@ size_t xdrg_index_workspace_size(uint64_t len, uint32_t max_msg_len);
  * element frames in the workspace) from where the chain stopped, then a
  * list-ranking window indexes the records after them up to the next long
  * one -- the call waits on the stream every round.  On a stream being
- * captured the walk runs alone, asynchronously: a stream it does not hold
- * gets the list ranking over records up to one window, which reports
- * XDRG_ERR_INDEX_LONG at a longer one (plans without the generated parse:
- * XDRG_EUNSUPPORTED).  Plans whose records can be empty are
+ * captured the rounds cannot run (they wait on the stream): the walk runs
+ * alone, asynchronously, with the list ranking over records up to one
+ * window behind it.  So a captured call indexes records past
+ * XDRG_INDEX_MAX_MSG only where the walk runs and holds: the stream must
+ * be at least 27776 bytes long (four 6944-byte segments; shorter streams
+ * are not walked) and good -- n records ending at len.  A captured stream
+ * shorter than 27776 bytes, or one the walk does not hold, gets the list
+ * ranking's answer, which reports XDRG_ERR_INDEX_LONG at the first record
+ * longer than XDRG_INDEX_MAX_MSG, where the same call outside a capture
+ * indexes it (plans without the generated parse: XDRG_EUNSUPPORTED under
+ * capture).  Plans whose records can be empty are
  * XDRG_EUNSUPPORTED.  Workspace: xdrg_index_workspace_size(len,
  * max_rec_len).
  */

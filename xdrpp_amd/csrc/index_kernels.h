@@ -267,10 +267,18 @@ struct rx_goff {
 //              merged into the true one, and no chain may break; the nodes
 //              from it on are the segment's records.  (A record that spans
 //              a whole segment passes only when the guess agrees.)  In a
-//              walk over records of any length (WHOLE) a segment that fails
-//              goes to rxs_fix instead.
-//   rxs_fix    (WHOLE) one wave re-decides the failed segments in stream
-//              order from the true entry (below).
+//              walk over records (LONG: the plan's generated parse, any
+//              max_rec_len) a segment that fails goes to rxs_fix instead;
+//              a walk over record marks clears the flag.
+//   rxs_fix    (records) one wave re-decides the failed segments in stream
+//              order from the true entry (below): up to kRxsFixCap of them
+//              in a walk over records of any length (WHOLE), where a miss
+//              costs rounds, and kRxsFixCapWindow in one over records up to
+//              the index window, where it costs one list ranking.  Without
+//              it one wrong guess in a stream sends all of it down the list
+//              ranking, and types whose records hold small integers next to
+//              their lengths (a counter as id, an empty string) offer such
+//              guesses at every record: tests/test_index_bands.py.
 //   (scan)     exclusive scan of those counts (launch_block_scan).
 //   rxs_emit   when the last exit is the stream's end and the chain holds
 //              exactly n records: offsets[] from the node lists, offsets[n]
@@ -719,10 +727,11 @@ __device__ __forceinline__ uint64_t rxs_verdict(const uint64_t *__restrict__ seg
 // the previous segment's exit -- r[3] = its index, cnt[i] = the segment's
 // records from it (for the scan); a segment where no record starts (the
 // previous exit at or past its end) is passed over (0, 0).  A segment whose
-// check fails clears the flag (the list ranking), except in a WHOLE walk
-// (LONG), where it goes to rxs_fix's list -- a guess that missed there is
-// expected: a look-back inside a long record's payload has no true chain to
-// follow -- and so does a segment whose exit passes over a whole segment
+// check fails clears the flag (the list ranking), except in a walk over
+// records (LONG), where it goes to rxs_fix's list -- a guess that missed is
+// expected there: a look-back inside a long record's payload has no true
+// chain to follow, and a word before a record's start may parse as a record
+// that joins the chain later -- and so does a segment whose exit passes over a whole segment
 // (the segments after it were passed over on its word).
 template <bool LONG = false>
 __device__ __forceinline__ void rxs_check_body(uint64_t *__restrict__ seg, const uint16_t *__restrict__ nodes,
@@ -750,7 +759,7 @@ __device__ __forceinline__ void rxs_check_body(uint64_t *__restrict__ seg, const
   if (!ok) *flag = 0u;
 }
 
-// rxs_fix (WHOLE walks): one wave, the listed segments in stream order, each
+// rxs_fix (walks over records): one wave, the listed segments in stream order, each
 // from its true entry: a segment the entry passes over is passed over (no
 // record starts there), one whose own walk holds the entry keeps its nodes,
 // and any other is walked again by the wave from it (nodes, count, exit);
@@ -761,9 +770,16 @@ __device__ __forceinline__ void rxs_check_body(uint64_t *__restrict__ seg, const
 // index stays exact.  Each segment it decides gets r[3] and cnt as
 // rxs_check's; a chain that does not parse, or a last segment that does not
 // end at the stream's end, clears the flag, and so do more than kRxsFixCap
-// listed segments (the list ranking).
+// listed segments (the list ranking).  maxlen is the walk's: a record past
+// it does not parse here either (RX_LONG), and the list ranking reports it.
 constexpr uint32_t kRxsFixBits = 1u << 18;  // segments the fix's LDS bitmap covers (1.8 GB of stream)
 constexpr uint64_t kRxsFixCap = 4096;       // listed segments it takes at most
+// ... and in a walk over records up to the index window (maxlen <=
+// XDRG_INDEX_MAX_MSG), where the list ranking that follows a miss is one
+// pass, not rounds: the wave decides a listed segment in a few
+// microseconds, one after another, so past a hundred or so the list
+// ranking is the faster answer
+constexpr uint64_t kRxsFixCapWindow = 128;
 template <class P>
 __device__ __forceinline__ void rxs_fix_body(const P &parser, const uint8_t *__restrict__ s, uint64_t len,
                                              uint32_t maxlen, uint64_t *__restrict__ seg, uint64_t nseg,
@@ -776,7 +792,8 @@ __device__ __forceinline__ void rxs_fix_body(const P &parser, const uint8_t *__r
   const uint32_t lane = threadIdx.x;
   const uint64_t c = *nl;
   if (c == 0) return;
-  if (nseg > kRxsFixBits || c > kRxsFixCap) {  // (the list ranking)
+  const uint64_t cap = maxlen > XDRG_INDEX_MAX_MSG ? kRxsFixCap : kRxsFixCapWindow;
+  if (nseg > kRxsFixBits || c > cap) {  // (the list ranking)
     if (lane == 0) *flag = 0u;
     return;
   }

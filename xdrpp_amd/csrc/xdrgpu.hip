@@ -2544,14 +2544,18 @@ int run_index(const xdrg_plan *p, const dev_tables *T, const void *d_stream, uin
       k_rxs_walk_msgs<<<ns, 64, 0, s>>>(s8, len, max_msg_len, seg, nodes, flag);
       HIPCHK(hipGetLastError());
     }
-    if (whole) {
+    // Records: the segments whose check fails go to rxs_fix (a guess that
+    // missed must not send the whole stream down the list ranking) -- in the
+    // walk over records up to max_msg_len too, where the fix parses with
+    // that bound and takes fewer segments (kRxsFixCapWindow)
+    if (whole || (REC && SM->f_rxs_fix)) {
       // the failed segments' list in the scan's output area (written after
       // the fix), its count a u64 at flag + 2 (zeroed by the walk)
       uint64_t *list = reinterpret_cast<uint64_t *>(base);
       auto *nl = reinterpret_cast<unsigned long long *>(flag + 2);
       k_rxs_check<true><<<(ns + 255) / 256, 256, 0, s>>>(seg, nodes, L.rxs_nseg, len, cnt, flag, list, nl);
       HIPCHK(hipGetLastError());
-      uint32_t ml = 0xffffffffu;
+      uint32_t ml = whole ? 0xffffffffu : max_msg_len;
       uint64_t nsg = L.rxs_nseg;
       void *jargs[] = {&s8, &len, &ml, &seg, &nsg, &nodes, &list, &nl, &flag, &cnt};
       HIPCHK(hipModuleLaunchKernel(static_cast<hipFunction_t>(SM->f_rxs_fix), 1, 1, 1, 64, 1, 1, 0, s, jargs,
