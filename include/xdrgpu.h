@@ -302,6 +302,35 @@ int xdrg_plan_create(const xdrg_op *ops, uint32_t nops, const uint32_t *table,
 void xdrg_plan_destroy(xdrg_plan *plan);
 int xdrg_plan_get_info(const xdrg_plan *plan, xdrg_plan_info *info);
 
+/* The shape of a fixed plan's encode (decode = 0) or decode program: what
+ * the launcher chooses its kernel by.  Host-only, launches nothing;
+ * XDRG_EUNSUPPORTED for a var plan.  With `path` of xdrg_plan_get_info:
+ *   FIXED_REG and 16-byte-aligned buffers: the register kernel (has_bool and
+ *     has_checks pick its instantiation, fixed_size / 16 its chunks per record);
+ *   otherwise, 16-byte-aligned buffers and no checks:
+ *     XDRG_OPT_FIXED_PATH 0, in_words and out_words <= 16, max_terms <= 2:
+ *       the tile kernel;
+ *     else XDRG_OPT_FIXED_PATH != 2, grp_G != 0 and n >= grp_G: the group
+ *       kernel (grp_KT terms per word) over the whole groups of grp_G
+ *       records, the LDS kernel over the n % grp_G records left;
+ *   everything else: the LDS kernel, which stages whole records and their
+ *     program in LDS: 4 * (in_words + 4) + 4 * roundup4(out_words) + 8 * nterms
+ *     bytes for one record, nterms at least the nonzero output words.  A plan
+ *     whose request exceeds the device's LDS per workgroup (160 KiB on
+ *     MI355X: records past about 40 KB) gets XDRG_EUNSUPPORTED from
+ *     xdrg_encode / xdrg_decode, and nothing is launched. */
+typedef struct xdrg_fixed_shape {
+  uint32_t in_words;   /* 4-byte words per input record  */
+  uint32_t out_words;  /* 4-byte words per output record */
+  uint32_t max_terms;  /* most terms (8-byte input windows or bools) of one output word */
+  uint32_t has_bool;   /* the program has bool terms */
+  uint32_t has_checks; /* decode program of a plan that validates pads or enums */
+  uint32_t grp_G;      /* group kernel: records per group (0: no group program) */
+  uint32_t grp_C;      /*   16-byte output chunks per group */
+  uint32_t grp_KT;     /*   terms per output word: 1, 2 or 4 */
+} xdrg_fixed_shape;
+int xdrg_plan_fixed_shape(const xdrg_plan *plan, int decode, xdrg_fixed_shape *out);
+
 /* Launch options of one plan (no reference counterpart: kernel choices and
  * launch shapes, for tests and tuning).  Every option defaults to the
  * automatic choice.  Options belong to the plan, not to the process; set
@@ -337,8 +366,10 @@ enum xdrg_plan_option {
                                      0 the record kernel that walks per window   */
   XDRG_OPT_FIXED_STREAM = 16,    /* identity fixed plans (k_fixed_reg) launch
                                      shape: -1 (default) by working set (in+out
-                                     past 384 MiB: non-temporal one-shot grid,
-                                     else plain 1024 workgroups); 0 plain 1024;
+                                     up to 256 MiB: plain loads and stores, 1024
+                                     workgroups; up to 1 GiB: non-temporal, 1024
+                                     workgroups; beyond: non-temporal, one chunk
+                                     per lane over a one-shot grid); 0 plain 1024;
                                      1 non-temporal one-shot; 2 plain one-shot;
                                      3 non-temporal 1024                         */
   XDRG_OPT_INDEX_FAST = 13        /* xdrg_index_records: 1 (default) the speculative

@@ -58,6 +58,9 @@ int main(void) {
   F(xdrg_plan_info, fixed_size); F(xdrg_plan_info, max_depth); F(xdrg_plan_info, nops);
   F(xdrg_plan_info, has_checks); F(xdrg_plan_info, max_record_bytes);
   F(xdrg_plan_info, group_records); F(xdrg_plan_info, specialized);
+  Z(xdrg_fixed_shape); F(xdrg_fixed_shape, in_words); F(xdrg_fixed_shape, out_words);
+  F(xdrg_fixed_shape, max_terms); F(xdrg_fixed_shape, has_bool); F(xdrg_fixed_shape, has_checks);
+  F(xdrg_fixed_shape, grp_G); F(xdrg_fixed_shape, grp_C); F(xdrg_fixed_shape, grp_KT);
   Z(xdrg_status); F(xdrg_status, first_error); F(xdrg_status, total_bytes);
   Z(xdrg_error); F(xdrg_error, code); F(xdrg_error, exc); F(xdrg_error, record);
   F(xdrg_error, op); F(xdrg_error, rsv); F(xdrg_error, total_bytes);
@@ -78,6 +81,7 @@ def test_struct_layouts(tmp_path):
                .stdout.splitlines())
     got = {k: int(v) for k, v in got.items()}
     mirrors = {"xdrg_op": A.XdrgOp, "xdrg_plan_info": A.XdrgPlanInfo,
+               "xdrg_fixed_shape": A.XdrgFixedShape,
                "xdrg_status": A.XdrgStatus, "xdrg_error": A.XdrgError}
     for cname, ct in mirrors.items():
         assert got[cname] == C.sizeof(ct), cname

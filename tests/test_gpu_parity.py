@@ -496,7 +496,7 @@ def test_record_depths_full_size(dev, name, n):
 
 
 # ------------------------------------- fixed non-identity paths (group / LDS)
-FIXED_PATHS = {"auto": 0, "lds": 2}
+FIXED_PATHS = {"auto": 0, "lds": 2, "group": 3}  # auto: the tile kernel for these two layouts
 BOOLS = S.Struct("boolrec", [("a", S.Bool), ("b", S.Bool), ("c", S.Int), ("d", S.Bool)])
 
 

@@ -98,6 +98,19 @@ class XdrgPlanInfo(C.Structure):
     ]
 
 
+class XdrgFixedShape(C.Structure):
+    _fields_ = [
+        ("in_words", C.c_uint32),
+        ("out_words", C.c_uint32),
+        ("max_terms", C.c_uint32),
+        ("has_bool", C.c_uint32),
+        ("has_checks", C.c_uint32),
+        ("grp_G", C.c_uint32),
+        ("grp_C", C.c_uint32),
+        ("grp_KT", C.c_uint32),
+    ]
+
+
 class XdrgStatus(C.Structure):
     _fields_ = [("first_error", C.c_uint64), ("total_bytes", C.c_uint64)]
 
@@ -124,7 +137,7 @@ EXPORTED = (
     "xdrg_rpc_replies", "xdrg_rpc_replies_workspace_size", "xdrg_record_depths",
     "xdrg_plan_set_option", "xdrg_plan_kernel_source", "xdrg_plan_build_kernels",
     "xdrg_plan_load_kernels", "xdrg_index_records", "xdrg_encode_sizes", "xdrg_encode_sized",
-    "xdrg_deep_workspace_size",
+    "xdrg_deep_workspace_size", "xdrg_plan_fixed_shape",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -164,6 +177,8 @@ def lib() -> C.CDLL:
     L.xdrg_plan_destroy.restype = None
     L.xdrg_plan_get_info.argtypes = [vp, C.POINTER(XdrgPlanInfo)]
     L.xdrg_plan_get_info.restype = C.c_int
+    L.xdrg_plan_fixed_shape.argtypes = [vp, C.c_int, C.POINTER(XdrgFixedShape)]
+    L.xdrg_plan_fixed_shape.restype = C.c_int
     L.xdrg_plan_set_option.argtypes = [vp, C.c_int, C.c_int64]
     L.xdrg_plan_set_option.restype = C.c_int
     L.xdrg_plan_kernel_source.argtypes = [vp, C.c_char_p, sz, C.POINTER(sz)]

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_fixed_lds(
     uint32_t nchecks, const uint32_t *__restrict__ table, unsigned long long *err) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t *tile = smem;                         // T*in_words (+4 pad)
-  const uint32_t tile_words = T * in_words + 4;  // multiple of 4 (T % 4 == 0)
+  const uint32_t tile_words = T * in_words + 4;  // (the tables after it need 4-byte alignment only)
   term_idx *sidx = reinterpret_cast<term_idx *>(smem + tile_words);
   term *sterms = reinterpret_cast<term *>(smem + tile_words + ((out_words + 3u) & ~3u));
   const uint32_t tid = threadIdx.x;

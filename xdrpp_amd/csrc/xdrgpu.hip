@@ -1585,6 +1585,44 @@ int launch_report(unsigned long long *err, uint64_t rec, uint32_t op, uint32_t c
   return XDRG_OK;
 }
 
+// LDS a workgroup of the current device may ask for (asked once per device;
+// 64 KiB where the device does not say).
+size_t lds_per_workgroup() {
+  static std::atomic<size_t> cached[kMaxDevices] = {};
+  constexpr size_t kDefault = 64u << 10;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return kDefault;
+  size_t v = cached[dev].load(std::memory_order_relaxed);
+  if (!v) {
+    int a = 0;
+    v = hipDeviceGetAttribute(&a, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && a > 0
+            ? size_t(a) : kDefault;
+    cached[dev].store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+
+// k_fixed_lds launch shape: records per tile and the LDS they take, which is
+//   4 * (TR * in_words + 4)  the tile and its 4 zero words
+//   + 4 * roundup4(out_words)  the term index
+//   + sizeof(term) * nterms    the terms.
+// TR is about 32 KiB of input records (4..256, a multiple of 4), fewer --
+// down to one -- where that exceeds the device's LDS per workgroup.  False
+// when not even one record fits.
+bool lds_shape(const fixed_prog &pg, uint32_t &TR, size_t &lds) {
+  const size_t rec = 4ull * pg.in_words;
+  const size_t prog = 16 + 4ull * ((pg.out_words + 3u) & ~3u) + sizeof(term) * pg.terms.size();
+  TR = std::min<uint32_t>(256, std::max<uint32_t>(4, 8192 / pg.in_words)) & ~3u;
+  const size_t limit = lds_per_workgroup();
+  if (TR * rec + prog > limit) {
+    if (rec + prog > limit) return false;
+    TR = uint32_t((limit - prog) / rec);
+    if (TR >= 4) TR &= ~3u;
+  }
+  lds = TR * rec + prog;
+  return true;
+}
+
 // Runs one fixed program (encode or decode) over nrec records.
 int run_fixed(const xdrg_plan &p, const dev_tables &T, bool decode, const void *in, void *out,
               uint64_t nrec, unsigned long long *err, hipStream_t s) {
@@ -1702,6 +1740,11 @@ int run_fixed(const xdrg_plan &p, const dev_tables &T, bool decode, const void *
       nrec >= pg.grp_G) {
     // Group path over the full groups; the tail (< G records) below.
     const uint64_t ngroups = nrec / pg.grp_G;
+    if (nrec % pg.grp_G) {  // nothing launches when the tail's kernel cannot
+      uint32_t tr = 0;
+      size_t bytes = 0;
+      if (!lds_shape(pg, tr, bytes)) return XDRG_EUNSUPPORTED;
+    }
     const uint64_t nchunks = ngroups * pg.grp_C;
     const uint32_t in_g = pg.grp_G * pg.in_words * 4u;
     const uint64_t cap = O.grp_blocks ? uint64_t(O.grp_blocks) : 2048u;
@@ -1735,13 +1778,11 @@ int run_fixed(const xdrg_plan &p, const dev_tables &T, bool decode, const void *
     nrec -= done;
   }
   const uint32_t in_words = pg.in_words, out_words = pg.out_words;
-  if (in_words > 8192) return XDRG_EUNSUPPORTED;  // > 32 KiB records: tile won't fit
-  uint32_t TR = std::min<uint32_t>(256, std::max<uint32_t>(4, 8192 / in_words));
-  TR &= ~3u;
+  uint32_t TR = 0;
+  size_t lds = 0;
+  if (!lds_shape(pg, TR, lds)) return XDRG_EUNSUPPORTED;  // one record and its program exceed the LDS
   const bool vec = aligned(in, 16) && aligned(out, 16) && (TR * in_words) % 4 == 0 &&
                    (TR * out_words) % 4 == 0;
-  const size_t lds = 4ull * (TR * in_words + 4) + 4ull * ((out_words + 3u) & ~3u) +
-                     sizeof(term) * pg.terms.size();
   const uint64_t tiles = (nrec + TR - 1) / TR;
   const uint64_t blocks = std::min<uint64_t>(tiles, 4096);
   const term_idx *idx = decode ? T.d_dec_idx : T.d_enc_idx;
@@ -2921,6 +2962,23 @@ int xdrg_plan_get_info(const xdrg_plan *p, xdrg_plan_info *info) {
   const bool failed_here = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kSpecDevices &&
                            p->spec.failed[dev].load();
   info->specialized = p->spec.state.load() == 1 && !failed_here ? 1u : 0u;
+  return XDRG_OK;
+}
+
+int xdrg_plan_fixed_shape(const xdrg_plan *p, int decode, xdrg_fixed_shape *out) {
+  if (!p || !out) return XDRG_EINVAL;
+  if (p->path == XDRG_PATH_VAR) return XDRG_EUNSUPPORTED;
+  const fixed_prog &pg = decode ? p->dec : p->enc;
+  uint32_t kt = 0;
+  for (const term_idx &ix : pg.idx) kt = std::max<uint32_t>(kt, ix.count);
+  out->in_words = pg.in_words;
+  out->out_words = pg.out_words;
+  out->max_terms = kt;
+  out->has_bool = pg.has_bool ? 1u : 0u;
+  out->has_checks = decode && p->has_checks ? 1u : 0u;
+  out->grp_G = pg.grp_G;
+  out->grp_C = pg.grp_C;
+  out->grp_KT = pg.grp_KT;
   return XDRG_OK;
 }
 
