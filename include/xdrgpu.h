@@ -32,6 +32,8 @@
  *   xdrg_rpc_check_replies <- check_call_hdr + xid test      xdrpp/rpc_msg.cc:115-131,
  *                                                            xdrpp/srpc.h:61-66
  *   xdrg_rpc_replies      <- rpc_*_msg error replies         xdrpp/server.cc:8-67
+ *   xdrg_rpc_verify_args  <- decode_arg per call             xdrpp/server.h:205-214,
+ *                                                            srpc.h:130-134
  *   xdrg_error_message    <- the what() strings of the exception types
  *                            xdrpp/types.h:57-99, marshal.h:104-108,152-170,
  *                            :131-136,:207-210, marshal.cc:43-57
@@ -66,7 +68,7 @@
 extern "C" {
 #endif
 
-#define XDRG_ABI_VERSION 8  /* 8: XDRG_SUB_FRAMES 32 -> 8 (register frames) */
+#define XDRG_ABI_VERSION 9  /* 9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
 
 /* ---------------------------------------------------------------------- */
 /* Plan ops: a flat, wire-ordered walk of xdr_traits<T>::save.             */
@@ -229,7 +231,8 @@ enum xdrg_err {
   XDRG_ERR_LOOKBACK = 19,      /* internal: a block of the one-pass encode waited
                                    too long for the byte total of the blocks before
                                    it (never expected; the output is not written) */
-  XDRG_ERR_INDEX_LONG = 20      /* xdrg_index_records: a record longer than its bound */
+  XDRG_ERR_INDEX_LONG = 20      /* xdrg_index_records: a record longer than its bound;
+                                   xdrg_verify: a record nested past XDRG_INDEX_FRAMES */
 };
 
 /* Exception class a data error maps to (for host-side rethrow). */
@@ -691,7 +694,7 @@ enum xdrg_rpc_action {          /* server side (xdrg_rpc_dispatch)             *
   XDRG_RPC_PROG_UNAVAIL = 4,    /* unknown prog                               server.cc:98-100 */
   XDRG_RPC_PROG_MISMATCH = 5,   /* unknown vers: low/high = registered range  server.cc:102-107 */
   XDRG_RPC_PROC_UNAVAIL = 6,    /* call_dispatch found no such proc           srpc.h:125-127 */
-  XDRG_RPC_GARBAGE_ARGS = 7,    /* set by the caller when the args fail       srpc.h:132-134, server.cc:109-116 */
+  XDRG_RPC_GARBAGE_ARGS = 7,    /* the args fail: xdrg_rpc_verify_args, or the caller  srpc.h:132-134, server.cc:109-116 */
   XDRG_RPC_SYSTEM_ERR = 8,      /* set by the caller (accept_stat SYSTEM_ERR) */
   XDRG_RPC_AUTH_ERROR = 9       /* set by the caller: why in w[2]             server.cc:42-53 */
 };
@@ -767,6 +770,105 @@ int xdrg_rpc_replies(const xdrg_rpc_hdr *d_hdrs, uint64_t n, void *d_out, uint64
                      uint64_t *d_offsets, void *d_workspace, size_t workspace_bytes,
                      xdrg_status *d_status, void *stream);
 size_t xdrg_rpc_replies_workspace_size(uint64_t n);
+
+/* ---------------------------------------------------------------------- */
+/* Per-record decode verdicts                                              */
+/* ---------------------------------------------------------------------- */
+/*
+ * xdrg_decode reports the lowest failing (record, op) of a batch, as one
+ * xdr_from_opaque over the concatenated stream would.  A server decodes
+ * every call's arguments on their own (decode_arg, xdrpp/server.h:205-214:
+ * archive(g, arg), g.done(), catch xdr_runtime_error): one bad record must
+ * not hide the others.  xdrg_verify runs the decode's walk over n spans of
+ * a stream with every check and no store, one verdict per span:
+ *
+ *   verdict: 0 = the record decodes; else (op << 8) | code, the low 24 bits
+ *   xdrg_status.first_error would hold; op 0xffff = record level
+ *
+ * The verdict of a span is what xdrg_decode reports for that record decoded
+ * alone (n = 1, offsets {begin, end}).  Span i is the byte range
+ * [*(d_begin + i * span_stride / 8), *(d_end + i * span_stride / 8));
+ * span_stride is a multiple of 8, at least 8.  With an offsets array,
+ * d_end = d_begin + 1 and the stride is 8; with RPC headers, &hdr[0].body_off,
+ * &hdr[0].end and 64.  Nothing outside [begin, end) is read.  Checks, in
+ * order:
+ *   end < begin or end > xdr_len      (op 0, XDRG_ERR_OVERFLOW_GET)
+ *   begin not a multiple of 4         the same verdict (xdrg_decode has no
+ *                                     such span: the records of a stream
+ *                                     start at multiples of 4); never read
+ *   (end - begin) not a multiple of 4 (0xffff, XDRG_ERR_SIZE_NOT_MULT4),
+ *                                     the xdr_get constructor (marshal.h:
+ *                                     157-159), fixed plans too
+ *   the ops in wire order             stack budget (XDRG_ERR_STACK_GET)
+ *                                     before space, then bounds, pads,
+ *                                     validated enums and discriminants; an
+ *                                     inline element fails at its element op
+ *   bytes left after the walk         (0xffff, XDRG_ERR_TRAILING)
+ * One kernel serves every plan (fixed, var, element subroutines): it
+ * interprets the plan's ops.  A lane keeps XDRG_INDEX_FRAMES element frames;
+ * a container that is the last field of its element and holds exactly one
+ * element opens none, so a pointer chain (rp__list) is verified at any
+ * length, bounded by stack_limit alone.  A record that needs more open
+ * frames gets (that VECTOR op, XDRG_ERR_INDEX_LONG): not decided here --
+ * decode it alone with xdrg_decode.
+ * *d_bad_count (may be NULL) = the spans with a nonzero verdict, zeroed by
+ * a kernel of the call and counted once per wave.  A plain launch: no
+ * workspace, no status block, capturable into a graph (run the plan's first
+ * launch on the device outside the capture).  Arguments are validated on
+ * the host before any HIP call: a NULL plan, NULL verdicts or spans with
+ * n > 0, or a bad stride is XDRG_EINVAL; n == 0 is XDRG_OK with nothing
+ * launched (*d_bad_count is left as it was).
+ */
+int xdrg_verify(const xdrg_plan *plan, const void *d_xdr, uint64_t xdr_len,
+                const uint64_t *d_begin, const uint64_t *d_end, uint32_t span_stride,
+                uint64_t n, uint32_t stack_limit, uint32_t *d_verdicts,
+                uint64_t *d_bad_count /* may be NULL */, void *stream);
+
+/*
+ * decode_arg for a whole dispatched batch, every procedure in one launch: a
+ * header whose action is XDRG_RPC_DISPATCH and whose (w[PROG], w[VERS],
+ * w[PROC]) is in `plans` has its arguments [body_off, end) verified with
+ * that procedure's plan, as xdrg_verify does.  A nonzero verdict sets
+ * action = XDRG_RPC_GARBAGE_ARGS and err = the code in place, so
+ * xdrg_rpc_replies writes the reply (server.cc:109-116); the other calls go
+ * on.  Every other header is untouched and gets verdict 0.  `plans` is a
+ * HOST array sorted by (prog, vers, proc) with no duplicates, at most
+ * XDRG_RPC_MAX_ARGPLANS entries: the plans' device tables travel as a
+ * kernel argument (no upload per call; capturable).  More procedures: several
+ * calls with disjoint tables.  nplans > XDRG_RPC_MAX_ARGPLANS, an unsorted
+ * or duplicate table or a NULL plan is XDRG_EINVAL before any HIP call.
+ */
+typedef struct xdrg_rpc_argplan {
+  uint32_t prog, vers, proc, rsv;
+  const xdrg_plan *plan; /* the procedure's arg_tuple_type as one record */
+} xdrg_rpc_argplan;
+#define XDRG_RPC_MAX_ARGPLANS 64u
+int xdrg_rpc_verify_args(const void *d_stream, uint64_t len, xdrg_rpc_hdr *d_hdrs, uint64_t n,
+                         const xdrg_rpc_argplan *plans, uint32_t nplans, uint32_t stack_limit,
+                         uint32_t *d_verdicts /* n, may be NULL */, void *stream);
+
+/*
+ * One procedure's arguments as an indexed stream: the headers with action
+ * XDRG_RPC_DISPATCH and (w[PROG], w[VERS], w[PROC]) == (prog, vers, proc),
+ * in message order.  d_index[k] = the message index of the k-th, d_offsets[k]
+ * = the offset of its argument bytes in d_args, d_offsets[count] = the
+ * total (also in d_status->total_bytes), *d_count = count; the bytes
+ * [body_off, end) are copied verbatim, at any length, so
+ * xdrg_decode(plan, d_args, total, d_offsets, count, ...) decodes them.  A
+ * header with end < body_off or end > len is skipped (not selected: nothing
+ * of the stream is read for it).  A capacity below the total is
+ * XDRG_ERR_OVERFLOW_PUT (record = the message index, op 0xffff) at the
+ * first message that does not fit; d_status is not initialised by the call
+ * (xdrg_status_init).  d_offsets holds n + 1 entries, d_index n; entries
+ * past count are unspecified.  Workspace:
+ * xdrg_rpc_gather_workspace_size(n) bytes.
+ */
+int xdrg_rpc_gather_args(const void *d_stream, uint64_t len, const xdrg_rpc_hdr *d_hdrs, uint64_t n,
+                         uint32_t prog, uint32_t vers, uint32_t proc,
+                         uint8_t *d_args, uint64_t args_capacity,
+                         uint64_t *d_offsets /* n+1 */, uint64_t *d_index /* n */, uint64_t *d_count,
+                         void *d_workspace, size_t workspace_bytes, xdrg_status *d_status, void *stream);
+size_t xdrg_rpc_gather_workspace_size(uint64_t n);
 
 /* Recursion depth per record: d_depths[i] = the deepest class/container
  * level record i's walk enters (the record itself is level 1), so

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libxdrgpu.s
 
 # enum xdrg_op_kind
 OP_U32, OP_U64, OP_BOOL, OP_ENUM, OP_OPAQUE, OP_VAROPAQUE, OP_STRING, OP_UNION, OP_JUMP, OP_END, OP_VECTOR = range(1, 12)
-ABI_VERSION = 8  # XDRG_ABI_VERSION, include/xdrgpu.h
+ABI_VERSION = 9  # XDRG_ABI_VERSION, include/xdrgpu.h
 F_VALIDATE = 1
 F_DEFAULT = 2
 F_POINTER = 4
@@ -138,6 +138,7 @@ EXPORTED = (
     "xdrg_plan_set_option", "xdrg_plan_kernel_source", "xdrg_plan_build_kernels",
     "xdrg_plan_load_kernels", "xdrg_index_records", "xdrg_encode_sizes", "xdrg_encode_sized",
     "xdrg_deep_workspace_size", "xdrg_plan_fixed_shape",
+    "xdrg_verify", "xdrg_rpc_verify_args", "xdrg_rpc_gather_args", "xdrg_rpc_gather_workspace_size",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -151,6 +152,15 @@ RPC_W_VERF_FLAVOR, RPC_W_LOW, RPC_W_HIGH = 5, 6, 7
 RPC_PROC_IFACE_ONLY = 1
 RPC_MAX_PROCS = 4096
 RPC_HDR_BYTES = 64
+RPC_MAX_ARGPLANS = 64  # XDRG_RPC_MAX_ARGPLANS
+INDEX_FRAMES = 16      # XDRG_INDEX_FRAMES: element frames a lane of xdrg_verify keeps
+VERDICT_RECORD_LEVEL = 0xFFFF  # op field of a record-level verdict
+
+
+class XdrgRpcArgplan(C.Structure):
+    _fields_ = [("prog", C.c_uint32), ("vers", C.c_uint32), ("proc", C.c_uint32), ("rsv", C.c_uint32),
+                ("plan", C.c_void_p)]
+
 
 _lib = None
 
@@ -221,6 +231,14 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_replies.restype = C.c_int
     L.xdrg_rpc_replies_workspace_size.argtypes = [u64]
     L.xdrg_rpc_replies_workspace_size.restype = sz
+    L.xdrg_verify.argtypes = [vp, vp, u64, vp, vp, u32, u64, u32, vp, vp, vp]
+    L.xdrg_verify.restype = C.c_int
+    L.xdrg_rpc_verify_args.argtypes = [vp, u64, vp, u64, C.POINTER(XdrgRpcArgplan), u32, u32, vp, vp]
+    L.xdrg_rpc_verify_args.restype = C.c_int
+    L.xdrg_rpc_gather_args.argtypes = [vp, u64, vp, u64, u32, u32, u32, vp, u64, vp, vp, vp, vp, sz, vp, vp]
+    L.xdrg_rpc_gather_args.restype = C.c_int
+    L.xdrg_rpc_gather_workspace_size.argtypes = [u64]
+    L.xdrg_rpc_gather_workspace_size.restype = sz
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

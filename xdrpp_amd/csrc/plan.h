@@ -181,6 +181,10 @@ int record_hip_error(int hip_error, const char *what);
 int fill32(void *p, uint32_t value, uint64_t words, void *stream);
 int copy_bytes(void *dst, const void *src, uint64_t n, void *stream);
 
+// The plan's tables on the current device (uploaded by the plan's first
+// launch there), for the launchers outside xdrgpu.hip (verify.hip).
+int plan_tables(const xdrg_plan *plan, const dev_tables **out);
+
 // Validates ops and builds all host-side programs.  Returns XDRG_OK or an
 // API error.  Does not touch the device.
 int compile_plan(xdrg_plan &p);

@@ -3294,3 +3294,7 @@ int xdrg_error_exception(int code) {
 }
 
 }  // extern "C"
+
+namespace xdrg {
+int plan_tables(const xdrg_plan *plan, const dev_tables **out) { return plan_upload(plan, out); }
+}  // namespace xdrg

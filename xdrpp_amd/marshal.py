@@ -148,6 +148,21 @@ def error_from(plan: Plan, e: A.XdrgError) -> XdrRuntimeError | None:
     return cls(what, int(e.record), op, int(e.code))
 
 
+def verdict_error(plan: Plan, verdict: int, record: int) -> XdrRuntimeError | None:
+    """The exception of one xdrg_verify verdict ((op << 8) | code, op 0xffff =
+    record level), as error_from builds it from a status block; None for
+    verdict 0 (the record decodes)."""
+    verdict = int(verdict)
+    if verdict == 0:
+        return None
+    e = A.XdrgError()
+    e.code = verdict & 0xFF
+    op = (verdict >> 8) & 0xFFFF
+    e.op = 0xFFFFFFFF if op == A.VERDICT_RECORD_LEVEL else op
+    e.record = int(record)
+    return error_from(plan, e)
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -352,6 +367,47 @@ class Marshaler:
         self.check(s)
         return native[:n * self.plan.stride], (None if heap is None else heap[:hsize])
 
+    def launch_verify(self, xdr, begin_ptr: int, end_ptr: int, span_stride: int, n: int, verdicts,
+                      bad_count=None, stack_limit=A.DEFAULT_STACK_LIMIT, stream=None):
+        """Raw xdrg_verify launch (no sync): spans from two device addresses
+        span_stride bytes apart; capturable into a graph."""
+        A.check(A.lib().xdrg_verify(
+            self.plan.handle, _ptr(xdr), xdr.numel(), begin_ptr, end_ptr, span_stride, n, stack_limit,
+            _ptr(verdicts), None if bad_count is None else bad_count.data_ptr(),
+            _stream() if stream is None else stream), "xdrg_verify")
+
+    def verify(self, xdr: torch.Tensor, offsets: torch.Tensor | None = None, *, begin: torch.Tensor | None = None,
+               end: torch.Tensor | None = None, n: int | None = None,
+               stack_limit: int = A.DEFAULT_STACK_LIMIT) -> tuple[torch.Tensor, int]:
+        """One decode verdict per record (xdrg_verify): what decode() would
+        raise for each record decoded alone, with nothing written.  Records
+        come from `offsets` (int64 [n + 1]), from `begin` / `end` (int64,
+        strided views of one tensor allowed: every k-th element), or, for a
+        fixed plan with neither, are the stream's n * fixed_size bytes.
+        Returns (verdicts int32 [n], bad_count): verdict 0 = decodes, else
+        (op << 8) | code (verdict_error makes the exception)."""
+        if offsets is not None:
+            cnt = offsets.numel() - 1
+            bp, ep, stride = offsets.data_ptr(), offsets.data_ptr() + 8, 8
+        elif begin is not None and end is not None:
+            if begin.dtype != torch.int64 or end.dtype != torch.int64 or begin.dim() != 1 or end.dim() != 1 or \
+                    begin.numel() != end.numel() or begin.stride(0) != end.stride(0) or begin.stride(0) < 1:
+                raise ValueError("begin and end: int64 vectors of one length and one stride")
+            cnt = begin.numel()
+            bp, ep, stride = begin.data_ptr(), end.data_ptr(), 8 * begin.stride(0)
+        elif self.plan.is_fixed:
+            cnt = xdr.numel() // self.plan.fixed_size if n is None else n
+            offsets = torch.arange(cnt + 1, dtype=torch.int64, device=self.device) * self.plan.fixed_size
+            bp, ep, stride = offsets.data_ptr(), offsets.data_ptr() + 8, 8
+        else:
+            raise ValueError("a var plan's records need offsets, or begin and end")
+        if n is not None and n != cnt:
+            raise ValueError("n disagrees with the spans given")
+        verdicts = torch.zeros(max(cnt, 1), dtype=torch.int32, device=self.device)
+        bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if cnt:
+            self.launch_verify(xdr, bp, ep, stride, cnt, verdicts, bad, stack_limit)
+        return verdicts[:cnt], int(bad.item())
 
     # ---- record-marked messages (message_t, RFC 5531) -----------------------
     def message_sizes(self, native, n, stack_limit=A.DEFAULT_STACK_LIMIT, heap=None) -> torch.Tensor:

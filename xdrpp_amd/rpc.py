@@ -11,6 +11,9 @@ Host-side mirror of the reference's RPC message handling, batched:
                                                             -> error_replies()
     xdr_to_msg(rpc_success_hdr(xid), res) (srpc.h:152)      -> success_reply_type()
                                                                + Marshaler.encode_msgs
+    decode_arg per call (server.h:205-214), GARBAGE_ARGS
+      for the calls that fail (srpc.h:130-134)              -> verify_args(), gather_args(),
+                                                               decode_args()
 
 Each header decodes to one 64-byte xdrg_rpc_hdr (HDR_DTYPE below).  The
 exceptions a client raises for a reply (xdr_call_error with the
@@ -24,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _abi as A
-from .marshal import Status, XdrRuntimeError, _EXC, _ptr, _stream
+from .marshal import Marshaler, Plan, Status, XdrRuntimeError, _EXC, _ptr, _stream
 from .xdr_types import Struct, UInt, XdrType
 
 HDR_DTYPE = np.dtype([("xid", "<u4"), ("action", "<u2"), ("err", "u1"), ("mtype", "u1"),
@@ -197,3 +200,88 @@ def success_reply_type(res: XdrType, name: str = "rpc_success_reply") -> Struct:
     constant words are staged fields (mtype=1, the rest 0)."""
     return Struct(name, [("xid", UInt), ("mtype", UInt), ("stat", UInt), ("flavor", UInt),
                          ("body", UInt), ("accept", UInt), ("res", res)])
+
+
+# ------------------------------------------------------- call arguments
+def _argplans(plans: dict) -> "C.Array":
+    import ctypes as C
+    if len(plans) > A.RPC_MAX_ARGPLANS:
+        raise ValueError(f"at most {A.RPC_MAX_ARGPLANS} procedures per call (several calls with disjoint tables)")
+    arr = (A.XdrgRpcArgplan * max(len(plans), 1))()
+    for i, key in enumerate(sorted(plans)):
+        prog, vers, proc = key
+        arr[i] = A.XdrgRpcArgplan(prog, vers, proc, 0, plans[key].handle)
+    return arr
+
+
+def verify_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tuple[int, int, int], Plan],
+                stack_limit: int = A.DEFAULT_STACK_LIMIT) -> torch.Tensor:
+    """decode_arg (server.h:205-214) for every dispatched call of the batch
+    whose (prog, vers, proc) is in `plans`, all procedures in one launch
+    (xdrg_rpc_verify_args).  A call whose arguments do not decode becomes
+    GARBAGE_ARGS with the error code in `err`, in place in `hdrs`, so
+    error_replies() answers it; the others go on.  Returns the verdicts
+    (int32 [n]; 0 for every header left untouched).  At most 64 procedures:
+    ValueError beyond."""
+    arr = _argplans(plans)
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    verdicts = torch.zeros(max(n, 1), dtype=torch.int32, device=hdrs.device)
+    A.check(A.lib().xdrg_rpc_verify_args(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), n, arr,
+                                         len(plans), stack_limit, _ptr(verdicts), _stream()),
+            "xdrg_rpc_verify_args")
+    return verdicts[:n]
+
+
+def gather_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, key: tuple[int, int, int],
+                capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The arguments of procedure key = (prog, vers, proc)'s dispatched calls
+    as one indexed stream, in message order (xdrg_rpc_gather_args): returns
+    (args uint8, offsets int64 [count + 1], index int64 [count] of message
+    numbers).  Marshaler.decode(args, count, offsets) decodes them.  One
+    sync, for the count and the total.  capacity: bytes of the output
+    (default: the stream's length, which always holds them); a smaller one
+    raises XdrRuntimeError (XDRG_ERR_OVERFLOW_PUT) with record = the first
+    message that does not fit."""
+    dev = hdrs.device
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    L = A.lib()
+    # (the arguments are disjoint pieces of the stream: its length holds them)
+    cap = stream_bytes.numel() if capacity is None else capacity
+    args = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    index = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(L.xdrg_rpc_gather_workspace_size(n), 16), dtype=torch.uint8, device=dev)
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    prog, vers, proc = key
+    A.check(L.xdrg_rpc_gather_args(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), n, prog, vers, proc,
+                                   args.data_ptr(), cap, offs.data_ptr(), index.data_ptr(), cnt.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), st.ptr, s), "xdrg_rpc_gather_args")
+    e = st.read(s)
+    if e.code:
+        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    count = int(cnt.item())
+    return args[:int(e.total_bytes)], offs[:count + 1], index[:count]
+
+
+def decode_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tuple[int, int, int], Plan],
+                stack_limit: int = A.DEFAULT_STACK_LIMIT) -> dict:
+    """The server's argument step for a dispatched batch: verify_args (the
+    calls that fail become GARBAGE_ARGS in `hdrs`), then per procedure
+    gather_args and Marshaler.decode of the calls left.  Returns
+    {key: (index, native, heap)}: the message numbers, and their decoded
+    records in that order."""
+    keys = sorted(plans)
+    for k0 in range(0, len(keys), A.RPC_MAX_ARGPLANS):
+        verify_args(stream_bytes, hdrs, {k: plans[k] for k in keys[k0:k0 + A.RPC_MAX_ARGPLANS]}, stack_limit)
+    out = {}
+    for key in keys:
+        args, offs, index = gather_args(stream_bytes, hdrs, key)
+        if index.numel() == 0:  # no call of this procedure is left
+            out[key] = (index, torch.empty(0, dtype=torch.uint8, device=hdrs.device), None)
+            continue
+        native, heap = Marshaler(plans[key], hdrs.device).decode(args, index.numel(), offs, stack_limit)
+        out[key] = (index, native, heap)
+    return out
