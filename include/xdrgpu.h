@@ -34,6 +34,10 @@
  *   xdrg_rpc_replies      <- rpc_*_msg error replies         xdrpp/server.cc:8-67
  *   xdrg_rpc_verify_args  <- decode_arg per call             xdrpp/server.h:205-214,
  *                                                            srpc.h:130-134
+ *   xdrg_rpc_match_replies <- rpc_sock::recv_msg: xid -> pending call
+ *                                                            xdrpp/msgsock.cc:202-232
+ *   xdrg_rpc_verify_results <- the reply callback of asynchronous_client_base::invoke
+ *                                                            xdrpp/arpc.h:59-90
  *   xdrg_error_message    <- the what() strings of the exception types
  *                            xdrpp/types.h:57-99, marshal.h:104-108,152-170,
  *                            :131-136,:207-210, marshal.cc:43-57
@@ -68,7 +72,8 @@
 extern "C" {
 #endif
 
-#define XDRG_ABI_VERSION 9  /* 9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
+#define XDRG_ABI_VERSION 10 /* 10: xdrg_rpc_match_replies, xdrg_rpc_verify_results, xdrg_rpc_gather_results;
+                               9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
 
 /* ---------------------------------------------------------------------- */
 /* Plan ops: a flat, wire-ordered walk of xdr_traits<T>::save.             */
@@ -705,7 +710,10 @@ enum xdrg_rpc_status {          /* client side (xdrg_rpc_check_replies)        *
   XDRG_RPCR_RPCVERS_MISMATCH = 3,/* xdr_call_error(RPCVERS_MISMATCH)  rpc_msg.cc:126 */
   XDRG_RPCR_NOT_REPLY = 4,      /* "call received when reply expected" rpc_msg.cc:117-118 */
   XDRG_RPCR_MALFORMED = 5,      /* archive(g, hdr) threw: code in err           srpc.h:62 */
-  XDRG_RPCR_BAD_XID = 6         /* "synchronous_client: unexpected xid"         srpc.h:64-65 */
+  XDRG_RPCR_BAD_XID = 6,        /* "synchronous_client: unexpected xid"         srpc.h:64-65 */
+  XDRG_RPCR_UNKNOWN_XID = 7,    /* "ignoring reply to unknown call" (xdrg_rpc_match_replies) msgsock.cc:212-216 */
+  XDRG_RPCR_GARBAGE_RES = 8     /* the reply does not unmarshal (xdrg_rpc_verify_results): code in err
+                                   arpc.h:87-89, rpc_msg.cc:89 */
 };
 /* w[] slots of xdrg_rpc_hdr */
 #define XDRG_RPC_W_RPCVERS 0     /* CALL  */
@@ -869,6 +877,112 @@ int xdrg_rpc_gather_args(const void *d_stream, uint64_t len, const xdrg_rpc_hdr 
                          uint64_t *d_offsets /* n+1 */, uint64_t *d_index /* n */, uint64_t *d_count,
                          void *d_workspace, size_t workspace_bytes, xdrg_status *d_status, void *stream);
 size_t xdrg_rpc_gather_workspace_size(uint64_t n);
+
+/* ---------------------------------------------------------------------- */
+/* Asynchronous client replies                                             */
+/* ---------------------------------------------------------------------- */
+/*
+ * xdrg_rpc_check_replies with d_xids is the synchronous client: one call
+ * outstanding, replies in order (xdrpp/srpc.h:61-66).  The reference's other
+ * client, asynchronous_client_base::invoke over rpc_sock (xdrpp/arpc.h:41-91,
+ * xdrpp/msgsock.cc:202-232), keeps a table of outstanding calls keyed by xid
+ * (rpc_sock::calls_) and takes replies in any order: it looks the xid up,
+ * drops a reply to an unknown call, erases the call, decodes the header,
+ * decodes the result with that call's result type, requires g.done(), and
+ * turns any xdr_runtime_error into GARBAGE_RES for that call alone.  The
+ * three calls below do this for a batch.
+ *
+ * A pending table is a device array of xdrg_rpc_call sorted by xid as
+ * unsigned, ascending, no duplicates.  `res` names the call's result type:
+ * an index into a host table of result plans.  An unsorted table is the
+ * caller's error: matches are then unspecified, but nothing outside the
+ * arrays is read or written.
+ */
+typedef struct xdrg_rpc_call { uint32_t xid; uint32_t res; } xdrg_rpc_call; /* 8 bytes */
+#define XDRG_RPC_NO_CALL 0xffffffffffffffffull
+
+/*
+ * rpc_sock::recv_msg (msgsock.cc:202-232) for every message of a batch.
+ * d_hdrs holds what xdrg_rpc_check_replies(..., d_xids = NULL, ...) wrote
+ * for the same batch.  The message itself is read, not the header record (a
+ * malformed header keeps no xid).  Per message, with body size
+ * d_offsets[i+1] - d_offsets[i] - 4:
+ *   size < 8             header untouched, d_call[i] = XDRG_RPC_NO_CALL (the
+ *                        reference's abort_all_calls is a connection matter
+ *                        and stays with the caller); so is a message whose
+ *                        offsets are not inside the stream (never read)
+ *   word 1 == CALL       header untouched (NOT_REPLY or MALFORMED), NO_CALL
+ *   word 1 == REPLY      binary search of word 0 in the table:
+ *     no entry           action = XDRG_RPCR_UNKNOWN_XID, NO_CALL
+ *                        ("ignoring reply to unknown call", msgsock.cc:212-216)
+ *     entry c            the lowest such message index i wins (the reference
+ *                        erases the call at its first reply, whether or not
+ *                        that reply decodes, msgsock.cc:217-219):
+ *                        d_call[i] = c, d_reply_of[c] = i, and its header
+ *                        keeps its action, MALFORMED included.  Every later
+ *                        reply to c becomes UNKNOWN_XID with NO_CALL
+ *   any other word 1     untouched, NO_CALL
+ * d_reply_of[c] = XDRG_RPC_NO_CALL for a call no message answers.  The
+ * outcome is a function of the inputs only: a fill, a 64-bit atomicMin of
+ * the message index into d_reply_of[c], then a kernel that compares.  No
+ * workspace, no status block, no memset node: capturable like xdrg_verify.
+ * ncalls == 0 is legal (d_calls may be NULL; every REPLY becomes
+ * UNKNOWN_XID).  n == 0 and ncalls == 0: XDRG_OK, nothing launched; n == 0
+ * and ncalls > 0: d_reply_of is filled with NO_CALL.  Validated on the host
+ * before any HIP call: NULL required pointers are XDRG_EINVAL, misaligned
+ * ones (headers 16, u64 arrays and calls 8, stream 4) XDRG_EALIGN.
+ */
+int xdrg_rpc_match_replies(const void *d_stream, uint64_t len, const uint64_t *d_offsets, uint64_t n,
+                           const xdrg_rpc_call *d_calls, uint64_t ncalls, xdrg_rpc_hdr *d_hdrs,
+                           uint64_t *d_call /* n */, uint64_t *d_reply_of /* ncalls */, void *stream);
+
+/*
+ * The body of the reply callback of arpc.h:59-90 for every matched reply,
+ * all result types in one launch.  `plans` is a HOST array of nplans <=
+ * XDRG_RPC_MAX_ARGPLANS plan pointers: plans[k] serves res == res_base + k; a
+ * NULL entry is a void result (xdr_void: a plan cannot be empty).  More
+ * result types: several calls with disjoint ranges.  A message is handled by
+ * the call whose range holds its call's res; it needs d_call[i] = c <
+ * ncalls.  By its action:
+ *   OK            [body_off, end) is verified exactly as xdrg_verify does
+ *                 (NULL plan: the span rules, then (0xffff, XDRG_ERR_TRAILING)
+ *                 when end > body_off).  A nonzero verdict sets action =
+ *                 XDRG_RPCR_GARBAGE_RES and err = the code (arpc.h:87-89)
+ *   ACCEPT_STAT, AUTH_STAT, RPCVERS_MISMATCH
+ *                 g.done() still runs (arpc.h:67-69): end != body_off is
+ *                 verdict (0xffff, XDRG_ERR_TRAILING), GARBAGE_RES, err =
+ *                 XDRG_ERR_TRAILING; else the header is untouched, verdict 0
+ *   MALFORMED     the header threw: GARBAGE_RES, err kept, verdict
+ *                 (0xffff << 8) | err
+ * Every other message is untouched, verdict 0.  The plans' device tables
+ * travel as a kernel argument, as in xdrg_rpc_verify_args (capturable; run
+ * each plan's first launch on the device outside the capture).  nplans >
+ * XDRG_RPC_MAX_ARGPLANS or NULL required pointers with n > 0 are XDRG_EINVAL
+ * before any HIP call.
+ */
+int xdrg_rpc_verify_results(const void *d_stream, uint64_t len, xdrg_rpc_hdr *d_hdrs,
+                            const uint64_t *d_call /* n */, uint64_t n,
+                            const xdrg_rpc_call *d_calls, uint64_t ncalls,
+                            const xdrg_plan *const *plans /* HOST, nplans */, uint32_t nplans,
+                            uint32_t res_base, uint32_t stack_limit,
+                            uint32_t *d_verdicts /* n, may be NULL */, void *stream);
+
+/*
+ * One result type's bytes as an indexed stream: xdrg_rpc_gather_args with the
+ * selection action == XDRG_RPCR_OK, d_call[i] = c < ncalls and
+ * d_calls[c].res == res, in message order.  d_index[k] = the message index of
+ * the k-th selected reply; d_results and d_offsets feed xdrg_decode.
+ * Capacity, skipped headers, d_status and the sizes of d_offsets and d_index
+ * are as in xdrg_rpc_gather_args.  Workspace:
+ * xdrg_rpc_gather_results_workspace_size(n) bytes.
+ */
+int xdrg_rpc_gather_results(const void *d_stream, uint64_t len, const xdrg_rpc_hdr *d_hdrs,
+                            const uint64_t *d_call /* n */, uint64_t n,
+                            const xdrg_rpc_call *d_calls, uint64_t ncalls, uint32_t res,
+                            uint8_t *d_results, uint64_t results_capacity,
+                            uint64_t *d_offsets /* n+1 */, uint64_t *d_index /* n */, uint64_t *d_count,
+                            void *d_workspace, size_t workspace_bytes, xdrg_status *d_status, void *stream);
+size_t xdrg_rpc_gather_results_workspace_size(uint64_t n);
 
 /* Recursion depth per record: d_depths[i] = the deepest class/container
  * level record i's walk enters (the record itself is level 1), so

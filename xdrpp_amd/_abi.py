@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libxdrgpu.s
 
 # enum xdrg_op_kind
 OP_U32, OP_U64, OP_BOOL, OP_ENUM, OP_OPAQUE, OP_VAROPAQUE, OP_STRING, OP_UNION, OP_JUMP, OP_END, OP_VECTOR = range(1, 12)
-ABI_VERSION = 9  # XDRG_ABI_VERSION, include/xdrgpu.h
+ABI_VERSION = 10  # XDRG_ABI_VERSION, include/xdrgpu.h
 F_VALIDATE = 1
 F_DEFAULT = 2
 F_POINTER = 4
@@ -139,13 +139,15 @@ EXPORTED = (
     "xdrg_plan_load_kernels", "xdrg_index_records", "xdrg_encode_sizes", "xdrg_encode_sized",
     "xdrg_deep_workspace_size", "xdrg_plan_fixed_shape",
     "xdrg_verify", "xdrg_rpc_verify_args", "xdrg_rpc_gather_args", "xdrg_rpc_gather_workspace_size",
+    "xdrg_rpc_match_replies", "xdrg_rpc_verify_results", "xdrg_rpc_gather_results",
+    "xdrg_rpc_gather_results_workspace_size",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
 RPC_DISPATCH, RPC_DROP_MALFORMED, RPC_DROP_NONCALL, RPC_RPC_MISMATCH, RPC_PROG_UNAVAIL, \
     RPC_PROG_MISMATCH, RPC_PROC_UNAVAIL, RPC_GARBAGE_ARGS, RPC_SYSTEM_ERR, RPC_AUTH_ERROR = range(10)
 RPCR_OK, RPCR_ACCEPT_STAT, RPCR_AUTH_STAT, RPCR_RPCVERS_MISMATCH, RPCR_NOT_REPLY, RPCR_MALFORMED, \
-    RPCR_BAD_XID = range(7)
+    RPCR_BAD_XID, RPCR_UNKNOWN_XID, RPCR_GARBAGE_RES = range(9)
 RPC_W_RPCVERS, RPC_W_PROG, RPC_W_VERS, RPC_W_PROC, RPC_W_CRED_FLAVOR = range(5)
 RPC_W_REPLY_STAT, RPC_W_STAT, RPC_W_WHY = range(3)
 RPC_W_VERF_FLAVOR, RPC_W_LOW, RPC_W_HIGH = 5, 6, 7
@@ -155,11 +157,17 @@ RPC_HDR_BYTES = 64
 RPC_MAX_ARGPLANS = 64  # XDRG_RPC_MAX_ARGPLANS
 INDEX_FRAMES = 16      # XDRG_INDEX_FRAMES: element frames a lane of xdrg_verify keeps
 VERDICT_RECORD_LEVEL = 0xFFFF  # op field of a record-level verdict
+RPC_NO_CALL = 0xFFFFFFFFFFFFFFFF  # XDRG_RPC_NO_CALL (-1 as int64)
+RPC_CALL_BYTES = 8                # sizeof(xdrg_rpc_call)
 
 
 class XdrgRpcArgplan(C.Structure):
     _fields_ = [("prog", C.c_uint32), ("vers", C.c_uint32), ("proc", C.c_uint32), ("rsv", C.c_uint32),
                 ("plan", C.c_void_p)]
+
+
+class XdrgRpcCall(C.Structure):
+    _fields_ = [("xid", C.c_uint32), ("res", C.c_uint32)]
 
 
 _lib = None
@@ -239,6 +247,14 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_gather_args.restype = C.c_int
     L.xdrg_rpc_gather_workspace_size.argtypes = [u64]
     L.xdrg_rpc_gather_workspace_size.restype = sz
+    L.xdrg_rpc_match_replies.argtypes = [vp, u64, vp, u64, vp, u64, vp, vp, vp, vp]
+    L.xdrg_rpc_match_replies.restype = C.c_int
+    L.xdrg_rpc_verify_results.argtypes = [vp, u64, vp, vp, u64, vp, u64, C.POINTER(vp), u32, u32, u32, vp, vp]
+    L.xdrg_rpc_verify_results.restype = C.c_int
+    L.xdrg_rpc_gather_results.argtypes = [vp, u64, vp, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp, vp, sz, vp, vp]
+    L.xdrg_rpc_gather_results.restype = C.c_int
+    L.xdrg_rpc_gather_results_workspace_size.argtypes = [u64]
+    L.xdrg_rpc_gather_results_workspace_size.restype = sz
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

@@ -1,0 +1,291 @@
+// The asynchronous client's reply step for a whole batch (replies.hip):
+// asynchronous_client_base::invoke over rpc_sock (xdrpp/arpc.h:41-91,
+// xdrpp/msgsock.cc:202-232) -- every reply is matched to its pending call by
+// xid, its result verified with that call's result type, and the results of
+// one type gathered for xdrg_decode.
+//
+//   k_reply_claim / k_reply_resolve   rpc_sock::recv_msg for every message:
+//       the message's own xid (word 0) and msg_type (word 1) are read, a
+//       REPLY's xid is looked up in the pending table (sorted by xid,
+//       unsigned: rpc_sock::calls_) by binary search, and the lowest message
+//       index that answers a call claims it with a 64-bit atomicMin
+//       (msgsock.cc:217-219 erases the call at its first reply); the second
+//       kernel compares: the winner keeps its header, every other reply to
+//       the call, and every reply to no call, becomes XDRG_RPCR_UNKNOWN_XID
+//       (msgsock.cc:212-216).  The outcome is a function of the inputs alone.
+//   k_rpc_verify_results   the reply callback of arpc.h:59-90, one matched
+//       reply per lane, each with its call's result plan: archive(g, *res),
+//       g.done(), and GARBAGE_RES for the reply that throws (arpc.h:87-89).
+//   k_gather_res_*   one result type's bytes as an indexed stream (the
+//       tiles, scan and coalesced emit of verify_kernels.h's k_gather_*).
+//
+// A header is rewritten through its first 16 bytes (xid, action | err |
+// mtype, w[0], w[1]): one 16-byte load, one 16-byte store when it changes.
+#pragma once
+// verify_kernels.h defines its three gather kernels as plain (external)
+// functions, and verify.hip already holds them: this translation unit gets
+// its own copies under other names.  k_gather_scan is launched from here too.
+#define k_gather_count k_gather_count_rtu
+#define k_gather_scan k_gather_scan_rtu
+#define k_gather_emit k_gather_emit_rtu
+#include "verify_kernels.h"
+
+namespace xdrg {
+namespace dev {
+
+constexpr unsigned long long kNoCall = XDRG_RPC_NO_CALL;
+// d_call between the two match kernels: a REPLY whose xid is in no entry
+constexpr unsigned long long kUnknownCall = XDRG_RPC_NO_CALL - 1u;
+constexpr uint32_t kMsgReply = 1;  // msg_type REPLY (rpc_msg.x)
+constexpr uint32_t kReplyThreads = 256;
+
+// The first 16 bytes of a header: action in the low half of word 1, err in
+// bits 16-23.
+__device__ __forceinline__ uint32_t hdr_action(const u32x4 &q) { return q.y & 0xffffu; }
+__device__ __forceinline__ uint32_t hdr_err(const u32x4 &q) { return (q.y >> 16) & 0xffu; }
+__device__ __forceinline__ void hdr_set(u32x4 &q, uint32_t action, uint32_t err) {
+  q.y = (q.y & 0xff000000u) | ((err & 0xffu) << 16) | action;
+}
+__device__ __forceinline__ u32x4 *hdr_head(xdrg_rpc_hdr *h) { return reinterpret_cast<u32x4 *>(h); }
+
+// The entry of the sorted table with this xid, or ncalls.  Stays inside
+// [0, ncalls) whatever the table holds.
+__device__ __forceinline__ uint64_t find_call(const xdrg_rpc_call *__restrict__ calls, uint64_t ncalls,
+                                              uint32_t xid) {
+  uint64_t lo = 0, hi = ncalls;
+  while (lo < hi) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (calls[mid].xid < xid) lo = mid + 1; else hi = mid;
+  }
+  return lo < ncalls && calls[lo].xid == xid ? lo : ncalls;
+}
+
+// One message per lane.  call[i] = the entry its xid names (claimed for the
+// lowest i by atomicMin), kUnknownCall for a REPLY to no entry, kNoCall for
+// everything that is no REPLY: a message shorter than xid + msg_type, a CALL,
+// another msg_type, or offsets that are no message of this stream (never
+// read).  reply_of[] was filled with kNoCall by the launch before this one.
+__global__ __launch_bounds__(kReplyThreads) void k_reply_claim(
+    const uint8_t *__restrict__ s, uint64_t len, const uint64_t *__restrict__ offs, uint64_t n,
+    const xdrg_rpc_call *__restrict__ calls, uint64_t ncalls, unsigned long long *__restrict__ call,
+    unsigned long long *__restrict__ reply_of) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kReplyThreads + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t m0 = offs[i], m1 = offs[i + 1];
+  unsigned long long c = kNoCall;
+  if (m1 <= len && m1 >= m0 && m1 - m0 >= 12u && !(m0 & 3u)) {
+    const uint32_t xid = bswap32(ld32(s + m0 + 4)), mtype = bswap32(ld32(s + m0 + 8));
+    if (mtype == kMsgReply) {
+      const uint64_t e = find_call(calls, ncalls, xid);
+      c = e < ncalls ? e : kUnknownCall;
+      if (e < ncalls) atomicMin(reply_of + e, static_cast<unsigned long long>(i));
+    }
+  }
+  call[i] = c;
+}
+
+// The compare: message i keeps entry c when it is the one that claimed it.
+__global__ __launch_bounds__(kReplyThreads) void k_reply_resolve(
+    xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n, unsigned long long *__restrict__ call,
+    const unsigned long long *__restrict__ reply_of) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kReplyThreads + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long c = call[i];
+  if (c == kNoCall) return;
+  if (c != kUnknownCall && reply_of[c] == i) return;  // the call's first reply
+  u32x4 *hp = hdr_head(hdrs + i);
+  u32x4 q = *hp;
+  hdr_set(q, XDRG_RPCR_UNKNOWN_XID, hdr_err(q));
+  *hp = q;
+  call[i] = kNoCall;
+}
+
+// ------------------------------------------------------- result verdicts
+// The span rules of verify_span for a void result (xdr_void: no bytes), then
+// g.done().
+__device__ __forceinline__ uint32_t verify_void(uint64_t len, uint64_t a, uint64_t b) {
+  if (b < a || b > len || (a & 3u)) return verdict_of(0, XDRG_ERR_OVERFLOW_GET);
+  if ((b - a) & 3u) return verdict_of(kOpRecordLevel, XDRG_ERR_SIZE_NOT_MULT4);
+  return b > a ? verdict_of(kOpRecordLevel, XDRG_ERR_TRAILING) : 0u;
+}
+
+// One header per lane.  T.e[k] serves the calls with res == res_base + k
+// (ops == nullptr: a void result; prog, vers and proc are not used).  The
+// table is searched by a wave-uniform loop, as in k_rpc_verify_args, and the
+// ops are staged the same way.
+template <bool SUB, bool LDSOPS>
+__global__ __launch_bounds__(SUB ? kVerifySubThreads : kVerifyThreads) void k_rpc_verify_results(
+    const uint8_t *__restrict__ xdr, uint64_t len, xdrg_rpc_hdr *__restrict__ hdrs,
+    const unsigned long long *__restrict__ call, uint64_t n, const xdrg_rpc_call *__restrict__ calls,
+    uint64_t ncalls, const verify_argtable T, uint32_t nplans, uint32_t res_base, uint32_t stack_limit,
+    uint32_t *__restrict__ verdicts) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t vsm[];
+  uint32_t *fbase = vsm;
+  if constexpr (LDSOPS) {
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < nplans; ++i) {
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(T.e[i].ops);
+      for (uint32_t k = threadIdx.x; k < 8u * T.e[i].nops; k += blockDim.x) vsm[8u * at + k] = src[k];
+      at += T.e[i].nops;
+    }
+    fbase = vsm + 8u * at;
+    __syncthreads();
+  }
+  const uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  uint32_t v = 0;
+  const unsigned long long c = call[r];
+  const uint32_t k = c < ncalls ? calls[c].res - res_base : nplans;
+  if (k < nplans) {
+    u32x4 *hp = hdr_head(hdrs + r);
+    u32x4 q = *hp;
+    const uint32_t action = hdr_action(q);
+    const uint64_t a = hdrs[r].body_off, b = hdrs[r].end;
+    uint32_t err = 0;
+    if (action == XDRG_RPCR_OK) {  // archive(g, *res); g.done()  (arpc.h:67-69)
+      const xdrg_op *ops = nullptr;
+      const uint32_t *table = nullptr;
+      uint32_t at = 0;
+      for (uint32_t i = 0; i < nplans; ++i) {
+        const bool hit = i == k && T.e[i].ops != nullptr;
+        ops = hit ? (LDSOPS ? reinterpret_cast<const xdrg_op *>(vsm) + at : T.e[i].ops) : ops;
+        table = hit ? T.e[i].table : table;
+        at += T.e[i].nops;
+      }
+      if (ops) {
+        using OPS = typename std::conditional<LDSOPS, lds_ops, glob_ops>::type;
+        const OPS O{ops};
+        if constexpr (SUB) {
+          lds_frames fr{fbase + threadIdx.x, blockDim.x};
+          v = verify_span(O, table, xdr, len, a, b, stack_limit, fr);
+        } else {
+          no_frames fr;
+          v = verify_span(O, table, xdr, len, a, b, stack_limit, fr);
+        }
+      } else {
+        v = verify_void(len, a, b);
+      }
+      err = v & 0xffu;
+    } else if (action == XDRG_RPCR_ACCEPT_STAT || action == XDRG_RPCR_AUTH_STAT ||
+               action == XDRG_RPCR_RPCVERS_MISMATCH) {  // no result, g.done() still runs
+      if (b != a) v = verdict_of(kOpRecordLevel, XDRG_ERR_TRAILING);
+      err = v & 0xffu;
+    } else if (action == XDRG_RPCR_MALFORMED) {  // archive(g, hdr) threw
+      err = hdr_err(q);
+      v = verdict_of(kOpRecordLevel, err);
+    }
+    if (v || action == XDRG_RPCR_MALFORMED) {  // cb(rpc_call_stat::GARBAGE_RES), arpc.h:87-89
+      hdr_set(q, XDRG_RPCR_GARBAGE_RES, err);
+      *hp = q;
+    }
+  }
+  if (verdicts) verdicts[r] = v;
+}
+
+// ---------------------------------------------------------- result gather
+struct gather_res_key {
+  const unsigned long long *call;
+  const xdrg_rpc_call *calls;
+  uint64_t ncalls;
+  uint32_t res;
+};
+
+// Selected: a matched reply that is still OK, of a call with this result
+// type, its result inside the stream.
+__device__ __forceinline__ bool gather_res_sel(const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t i, uint64_t n,
+                                               uint64_t len, const gather_res_key &K, uint64_t *src,
+                                               uint64_t *bytes) {
+  *src = 0;
+  *bytes = 0;
+  if (i >= n) return false;
+  const xdrg_rpc_hdr *h = hdrs + i;
+  if (h->action != XDRG_RPCR_OK) return false;
+  const unsigned long long c = K.call[i];
+  if (c >= K.ncalls || K.calls[c].res != K.res) return false;
+  const uint64_t a = h->body_off, b = h->end;
+  if (b < a || b > len) return false;
+  *src = a;
+  *bytes = b - a;
+  return true;
+}
+
+__global__ __launch_bounds__(kGatherThreads) void k_gather_res_count(
+    const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n, uint64_t len, gather_res_key K,
+    unsigned long long *__restrict__ tile_cnt, unsigned long long *__restrict__ tile_bytes) {
+  __shared__ unsigned long long wc[kGatherThreads / 64], wb[kGatherThreads / 64];
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kGatherThreads + threadIdx.x;
+  uint64_t src, bytes;
+  const bool sel = gather_res_sel(hdrs, i, n, len, K, &src, &bytes);
+  unsigned long long c = sel ? 1u : 0u, t = bytes;
+  for (int o = 32; o > 0; o >>= 1) {
+    c += __shfl_xor(c, o, 64);
+    t += __shfl_xor(t, o, 64);
+  }
+  if ((threadIdx.x & 63u) == 0u) { wc[threadIdx.x >> 6] = c; wb[threadIdx.x >> 6] = t; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long sc = 0, sb = 0;
+    for (uint32_t k = 0; k < kGatherThreads / 64; ++k) { sc += wc[k]; sb += wb[k]; }
+    tile_cnt[blockIdx.x] = sc;
+    tile_bytes[blockIdx.x] = sb;
+  }
+}
+
+// k_gather_emit with the result selection: index and offsets a lane per
+// header, the bytes a wave per run of 64 headers, 4 bytes a lane per step.
+__global__ __launch_bounds__(kGatherThreads) void k_gather_res_emit(
+    const uint8_t *__restrict__ xdr, uint64_t len, const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n,
+    gather_res_key K, uint8_t *__restrict__ out, uint64_t cap, uint64_t *__restrict__ offsets,
+    uint64_t *__restrict__ index, const unsigned long long *__restrict__ tile_cnt,
+    const unsigned long long *__restrict__ tile_bytes, unsigned long long *err) {
+  __shared__ unsigned long long wc[kGatherThreads / 64], wb[kGatherThreads / 64];
+  __shared__ unsigned long long s_end[kGatherThreads], s_src[kGatherThreads];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kGatherThreads + tid;
+  uint64_t src, bytes;
+  const bool sel = gather_res_sel(hdrs, i, n, len, K, &src, &bytes);
+  const uint64_t ic = wave_incl_scan64(sel ? 1u : 0u), ib = wave_incl_scan64(bytes);
+  if (lane == 63u) { wc[wid] = ic; wb[wid] = ib; }
+  __syncthreads();
+  uint64_t kbase = tile_cnt[blockIdx.x], wbase = tile_bytes[blockIdx.x];
+  for (uint32_t k = 0; k < wid; ++k) { kbase += wc[k]; wbase += wb[k]; }
+  const uint64_t at = wbase + ib - bytes;  // wbase: where the wave's stretch starts
+  bool fits = false;
+  if (sel) {
+    const uint64_t k = kbase + ic - 1u;
+    index[k] = i;
+    offsets[k] = at;
+    fits = at <= cap && bytes <= cap - at;
+    if (!fits) {  // xdr_generic_put::check (marshal.h:104-108)
+      const unsigned long long key = (static_cast<unsigned long long>(i) << 24) |
+                                     (static_cast<unsigned long long>(kOpRecordLevel) << 8) | XDRG_ERR_OVERFLOW_PUT;
+      atomicMin(err, key);
+    }
+  }
+  // the results that fit are a prefix of the wave's stretch
+  const uint64_t cb = fits ? bytes : 0u;
+  const uint64_t ie = wave_incl_scan64(cb);
+  unsigned long long *w_end = s_end + 64u * wid, *w_src = s_src + 64u * wid;
+  w_end[lane] = ie;
+  w_src[lane] = src;
+  const bool words = __ballot(fits && ((src | bytes) & 3u)) == 0ull &&
+                     !((reinterpret_cast<uintptr_t>(xdr) | (reinterpret_cast<uintptr_t>(out) + wbase)) & 3u);
+  __syncthreads();
+  const uint64_t total = w_end[63];
+  const uint32_t unit = words ? 4u : 1u;
+  for (uint64_t off = static_cast<uint64_t>(lane) * unit; off < total; off += 64u * unit) {
+    uint32_t lo = 0, hi = 63;  // the first message whose end is past `off`
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (w_end[mid] > off) hi = mid; else lo = mid + 1;
+    }
+    const uint64_t start = lo ? w_end[lo - 1] : 0u;
+    const uint8_t *s = xdr + w_src[lo] + (off - start);
+    uint8_t *d = out + wbase + off;
+    if (words) st32(d, ld32(s));
+    else *d = *s;
+  }
+}
+
+}  // namespace dev
+}  // namespace xdrg

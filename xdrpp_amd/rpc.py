@@ -14,12 +14,19 @@ Host-side mirror of the reference's RPC message handling, batched:
     decode_arg per call (server.h:205-214), GARBAGE_ARGS
       for the calls that fail (srpc.h:130-134)              -> verify_args(), gather_args(),
                                                                decode_args()
+    rpc_sock::recv_msg (msgsock.cc:202-232): replies in any
+      order joined to the pending calls by xid              -> PendingCalls, match_replies()
+    the reply callback of asynchronous_client_base::invoke
+      (arpc.h:59-90): result + g.done(), GARBAGE_RES for
+      the reply that throws                                 -> verify_results(), gather_results(),
+                                                               decode_results()
+    xdr_to_msg(hdr, a...) of a call (arpc.h:44-59)          -> call_type() + Marshaler.encode_msgs
 
 Each header decodes to one 64-byte xdrg_rpc_hdr (HDR_DTYPE below).  The
 exceptions a client raises for a reply (xdr_call_error with the
 rpc_call_stat message, exception.h:25-57, rpc_msg.cc:8-109) come from
 raise_for_reply().  Every byte is produced by the HIP kernels of
-libxdrgpu.so (xdrpp_amd/csrc/rpc.hip).
+libxdrgpu.so (xdrpp_amd/csrc/rpc.hip, verify.hip, replies.hip).
 """
 from __future__ import annotations
 
@@ -285,3 +292,220 @@ def decode_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tupl
         native, heap = Marshaler(plans[key], hdrs.device).decode(args, index.numel(), offs, stack_limit)
         out[key] = (index, native, heap)
     return out
+
+
+# ------------------------------------------------ the asynchronous client
+CALL_DTYPE = np.dtype([("xid", "<u4"), ("res", "<u4")])
+assert CALL_DTYPE.itemsize == A.RPC_CALL_BYTES
+
+
+def call_type(args: XdrType | None = None, name: str = "rpc_call") -> Struct:
+    """The record xdr_to_msg(hdr, a...) marshals for a call (arpc.h:44-59,
+    srpc.cc:71-80): the call header's ten words -- xid, mtype = CALL (0),
+    rpcvers = 2, prog, vers, proc and two AUTH_NONE opaque_auth with empty
+    bodies (flavor 0, length 0) -- as staged fields, then the argument
+    record.  args=None: a procedure without arguments."""
+    fields = [(f, UInt) for f in ("xid", "mtype", "rpcvers", "prog", "vers", "proc",
+                                  "cred_flavor", "cred_len", "verf_flavor", "verf_len")]
+    if args is not None:
+        fields.append(("args", args))
+    return Struct(name, fields)
+
+
+class PendingCalls:
+    """rpc_sock::calls_ (msgsock.h) for a batch: the outstanding calls keyed
+    by xid, each with `res`, the number of its result type.  Sorts by xid as
+    unsigned (the table xdrg_rpc_match_replies searches), raises ValueError on
+    a duplicate xid, and keeps the device table and the permutation, so that
+    everything the functions below take and return names a call by its
+    position in `xids`."""
+
+    def __init__(self, xids, res, device="cuda"):
+        if isinstance(xids, torch.Tensor):
+            xids = xids.cpu().numpy()
+        if isinstance(res, torch.Tensor):
+            res = res.cpu().numpy()
+        x = (np.asarray(xids).astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32)
+        r = np.broadcast_to(np.asarray(res).astype(np.int64) & 0xFFFFFFFF, x.shape).astype(np.uint32)
+        order = np.argsort(x, kind="stable")
+        xs = x[order]
+        if np.any(xs[1:] == xs[:-1]):
+            raise ValueError("PendingCalls: duplicate xid")
+        t = np.empty(x.size, dtype=CALL_DTYPE)
+        t["xid"], t["res"] = xs, r[order]
+        inv = np.empty(x.size, dtype=np.int64)
+        inv[order] = np.arange(x.size, dtype=np.int64)
+        self.device = torch.device(device)
+        self.ncalls = int(x.size)
+        self.calls = t                                                  # host copy, sorted
+        self.table = torch.from_numpy(t.view(np.int64).copy()).to(self.device)  # xdrg_rpc_call [ncalls]
+        self.perm = torch.from_numpy(order.astype(np.int64)).to(self.device)    # table position -> caller's
+        self.inv = torch.from_numpy(inv).to(self.device)                        # caller's -> table position
+
+    def to_caller(self, call: torch.Tensor) -> torch.Tensor:
+        """d_call (table positions, -1 for none) in the caller's positions."""
+        if self.ncalls == 0:
+            return call
+        return torch.where(call >= 0, self.perm[call.clamp(min=0)], call)
+
+    def to_table(self, call: torch.Tensor) -> torch.Tensor:
+        if self.ncalls == 0:
+            return call
+        return torch.where(call >= 0, self.inv[call.clamp(min=0)], call)
+
+
+def launch_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, pending: PendingCalls,
+                         hdrs: torch.Tensor, call: torch.Tensor, reply_of: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_match_replies as it is: `call` int64 [n] and `reply_of` int64
+    [ncalls] in TABLE positions (pending.to_caller converts).  Kernels only:
+    capturable."""
+    n = offsets.numel() - 1
+    A.check(A.lib().xdrg_rpc_match_replies(_ptr(stream_bytes), stream_bytes.numel(), _ptr(offsets), n,
+                                           _ptr(pending.table), pending.ncalls, _ptr(hdrs), _ptr(call),
+                                           _ptr(reply_of), _stream() if stream is None else stream),
+            "xdrg_rpc_match_replies")
+
+
+def match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor,
+                  pending: PendingCalls) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """rpc_sock::recv_msg (msgsock.cc:202-232) for every message: runs
+    check_replies without xids, then joins the replies to the pending calls.
+    Returns (hdrs, call int64 [n], reply_of int64 [ncalls]): call[i] = the
+    call message i answers, reply_of[c] = the message that answers call c, -1
+    for none.  The first reply to a call wins; every other reply to it, and
+    every reply to no pending call, has action RPCR_UNKNOWN_XID."""
+    dev = stream_bytes.device
+    n = offsets.numel() - 1
+    hdrs = check_replies(stream_bytes, offsets)
+    call = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    reply_of = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=dev)
+    launch_match_replies(stream_bytes, offsets, pending, hdrs, call, reply_of)
+    reply_of = reply_of[:pending.ncalls]
+    return hdrs, pending.to_caller(call[:n]), reply_of[pending.inv] if pending.ncalls else reply_of
+
+
+def _res_runs(plans: dict) -> list[list[int]]:
+    """The result numbers of `plans` as runs of consecutive numbers, at most
+    RPC_MAX_ARGPLANS long: one xdrg_rpc_verify_results call each (a number
+    inside a call's range without a plan would be taken for void)."""
+    runs: list[list[int]] = []
+    for k in sorted(plans):
+        if runs and k == runs[-1][-1] + 1 and len(runs[-1]) < A.RPC_MAX_ARGPLANS:
+            runs[-1].append(k)
+        else:
+            runs.append([k])
+    return runs
+
+
+def launch_verify_results(stream_bytes: torch.Tensor, hdrs: torch.Tensor, call: torch.Tensor,
+                          pending: PendingCalls, plans: list, res_base: int, stack_limit: int,
+                          verdicts: torch.Tensor | None, stream=None) -> None:
+    """xdrg_rpc_verify_results as it is: `call` in TABLE positions, plans[k]
+    (a Plan, or None for void) serves res == res_base + k."""
+    import ctypes as C
+    arr = (C.c_void_p * max(len(plans), 1))(*[None if p is None else p.handle for p in plans])
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    A.check(A.lib().xdrg_rpc_verify_results(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), _ptr(call), n,
+                                            _ptr(pending.table), pending.ncalls, arr, len(plans), res_base,
+                                            stack_limit, _ptr(verdicts), _stream() if stream is None else stream),
+            "xdrg_rpc_verify_results")
+
+
+def _verify_results_t(stream_bytes, hdrs, tcall, pending, plans, stack_limit):
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    total = torch.zeros(max(n, 1), dtype=torch.int32, device=hdrs.device)
+    for run in _res_runs(plans):
+        v = torch.zeros(max(n, 1), dtype=torch.int32, device=hdrs.device)
+        launch_verify_results(stream_bytes, hdrs, tcall, pending, [plans[k] for k in run], run[0], stack_limit, v)
+        total |= v  # a message is in one call's range
+    return total[:n]
+
+
+def verify_results(stream_bytes: torch.Tensor, hdrs: torch.Tensor, call: torch.Tensor, pending: PendingCalls,
+                   plans: dict[int, Plan | None], stack_limit: int = A.DEFAULT_STACK_LIMIT) -> torch.Tensor:
+    """The reply callback of arpc.h:59-90 for every matched reply
+    (xdrg_rpc_verify_results): plans[res] is the result type's Plan, None for
+    a void result.  A reply whose result does not decode, that has bytes
+    left after it (g.done()), or whose header threw becomes RPCR_GARBAGE_RES
+    with the code in `err`, in place in `hdrs`.  Returns the verdicts (int32
+    [n]; 0 for every header left untouched).  `call` is match_replies()'s."""
+    return _verify_results_t(stream_bytes, hdrs, pending.to_table(call), pending, plans, stack_limit)
+
+
+def _gather_results_t(stream_bytes, hdrs, tcall, pending, res, capacity=None):
+    dev = hdrs.device
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    L = A.lib()
+    cap = stream_bytes.numel() if capacity is None else capacity
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    index = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(L.xdrg_rpc_gather_results_workspace_size(n), 16), dtype=torch.uint8, device=dev)
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    A.check(L.xdrg_rpc_gather_results(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), _ptr(tcall), n,
+                                      _ptr(pending.table), pending.ncalls, res, out.data_ptr(), cap,
+                                      offs.data_ptr(), index.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      st.ptr, s), "xdrg_rpc_gather_results")
+    e = st.read(s)
+    if e.code:
+        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    count = int(cnt.item())
+    return out[:int(e.total_bytes)], offs[:count + 1], index[:count]
+
+
+def gather_results(stream_bytes: torch.Tensor, hdrs: torch.Tensor, call: torch.Tensor, pending: PendingCalls,
+                   res: int, capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The results of type `res` of the matched replies that are RPCR_OK, as
+    one indexed stream in message order (xdrg_rpc_gather_results): returns
+    (bytes uint8, offsets int64 [count + 1], index int64 [count] of message
+    numbers), as gather_args does for a procedure's arguments."""
+    return _gather_results_t(stream_bytes, hdrs, pending.to_table(call), pending, res, capacity)
+
+
+def decode_results(stream_bytes: torch.Tensor, offsets: torch.Tensor, pending: PendingCalls,
+                   plans: dict[int, Plan | None], stack_limit: int = A.DEFAULT_STACK_LIMIT):
+    """The client's reply step in one call: match_replies, verify_results
+    (the replies that fail become GARBAGE_RES), then per result type
+    gather_results and Marshaler.decode of the replies left.  Returns (hdrs,
+    call, reply_of, {res: (index, native, heap)}); a void result type has
+    native = heap = None."""
+    dev = stream_bytes.device
+    n = offsets.numel() - 1
+    hdrs = check_replies(stream_bytes, offsets)
+    tcall = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    reply_of = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=dev)
+    launch_match_replies(stream_bytes, offsets, pending, hdrs, tcall, reply_of)
+    tcall, reply_of = tcall[:n], reply_of[:pending.ncalls]
+    _verify_results_t(stream_bytes, hdrs, tcall, pending, plans, stack_limit)
+    out = {}
+    for res in sorted(plans):
+        data, offs, index = _gather_results_t(stream_bytes, hdrs, tcall, pending, res)
+        if plans[res] is None:
+            out[res] = (index, None, None)
+        elif index.numel() == 0:
+            out[res] = (index, torch.empty(0, dtype=torch.uint8, device=dev), None)
+        else:
+            native, heap = Marshaler(plans[res], dev).decode(data, index.numel(), offs, stack_limit)
+            out[res] = (index, native, heap)
+    return hdrs, pending.to_caller(tcall), reply_of[pending.inv] if pending.ncalls else reply_of, out
+
+
+def call_stat_message(h) -> str:
+    """rpc_call_stat::message() (rpc_msg.cc:92-112) of the call_result a reply
+    header stands for after verify_results (rpc_call_stat(hdr), rpc_msg.cc:
+    69-90; the catch of arpc.h:87-89)."""
+    a = int(h["action"])
+    if a == A.RPCR_OK:
+        return rpc_errmsg_accept(0)
+    if a == A.RPCR_ACCEPT_STAT:
+        return rpc_errmsg_accept(int(h["w"][A.RPC_W_STAT]))
+    if a == A.RPCR_AUTH_STAT:
+        return rpc_errmsg_auth(int(h["w"][A.RPC_W_WHY]))
+    if a == A.RPCR_RPCVERS_MISMATCH:
+        return "server reported rpcvers field with wrong value"
+    if a in (A.RPCR_GARBAGE_RES, A.RPCR_MALFORMED, A.RPCR_NOT_REPLY):
+        return "unable to unmarshal reply value sent by server"
+    raise ValueError("no call stands behind this reply (ignoring reply to unknown call)")
