@@ -38,7 +38,9 @@
  *                                                            xdrpp/msgsock.cc:202-232
  *   xdrg_rpc_verify_results <- the reply callback of asynchronous_client_base::invoke
  *                                                            xdrpp/arpc.h:59-90
- *   xdrg_error_message    <- the what() strings of the exception types
+ *   xdrg_rpc_reply_batch  <- srpc_service::dispatch's reply, srpc.h:130-153; the
+ *   (+ _workspace_size)      order srpc_server::run writes them in, srpc.cc:83-88
+ *   xdrg_error_message   <- the what() strings of the exception types
  *                            xdrpp/types.h:57-99, marshal.h:104-108,152-170,
  *                            :131-136,:207-210, marshal.cc:43-57
  *
@@ -73,6 +75,7 @@ extern "C" {
 #endif
 
 #define XDRG_ABI_VERSION 10 /* 10: xdrg_rpc_match_replies, xdrg_rpc_verify_results, xdrg_rpc_gather_results;
+                                   (additive, still 10) xdrg_rpc_reply_batch, xdrg_rpc_reply_batch_workspace_size;
                                9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
 
 /* ---------------------------------------------------------------------- */
@@ -983,6 +986,89 @@ int xdrg_rpc_gather_results(const void *d_stream, uint64_t len, const xdrg_rpc_h
                             uint64_t *d_offsets /* n+1 */, uint64_t *d_index /* n */, uint64_t *d_count,
                             void *d_workspace, size_t workspace_bytes, xdrg_status *d_status, void *stream);
 size_t xdrg_rpc_gather_results_workspace_size(uint64_t n);
+
+/* ---------------------------------------------------------------------- */
+/* Server reply batch                                                      */
+/* ---------------------------------------------------------------------- */
+/*
+ * srpc_server::run (xdrpp/srpc.cc:83-88) reads a message, dispatches it and
+ * writes its reply before it reads the next one: the socket carries one reply
+ * per answered call, in call order -- xdr_to_msg(rpc_success_hdr(xid), *res)
+ * (srpc.h:152, server.h:27-49) for a call that was served, one of the
+ * rpc_*_msg replies (server.cc:8-67) for a call that failed.
+ * xdrg_rpc_reply_batch writes that stream for a dispatched batch whose
+ * handlers have run: the results come as up to XDRG_RPC_MAX_RESULT_SRCS
+ * sources, each the output of one xdrg_encode and the message every result
+ * answers (xdrg_rpc_gather_args' d_index).
+ *
+ * Message i, in message order:
+ *   action RPC_MISMATCH, PROG_UNAVAIL, PROG_MISMATCH, PROC_UNAVAIL,
+ *   GARBAGE_ARGS, SYSTEM_ERR, AUTH_ERROR
+ *                  exactly the bytes xdrg_rpc_replies writes for the header.
+ *                  A result that names such a message is not used.
+ *   DISPATCH with a winning entry
+ *                  the mark BE((24 + L) | XDRG_MARK_LAST), the six words xid,
+ *                  REPLY (1), MSG_ACCEPTED (0), AUTH_NONE (0), 0, SUCCESS (0)
+ *                  big-endian, then the entry's L result bytes verbatim (a
+ *                  void result: L = 0, 28 bytes).  The result bytes are not
+ *                  validated as XDR: the server trusts its own encoder.
+ *   DISPATCH with no entry (an asynchronous service that has not answered
+ *   yet), DROP_*, any other action
+ *                  no reply: d_offsets[i] == d_offsets[i+1].
+ * Entry k of a source, k < min(*d_count, count_cap), names message
+ * d_index[k] and holds the bytes [d_offsets[k], d_offsets[k+1]) of d_bytes
+ * (d_offsets NULL: [k * fixed_size, (k+1) * fixed_size); d_bytes NULL: no
+ * bytes, and d_offsets is not read).  An entry is not usable, and nothing of
+ * d_bytes is read for it, when index >= n, when its message's action is not
+ * DISPATCH, when its span has end < begin or end > bytes_len, when its offset
+ * or length is not a multiple of 4, or when 24 + L > XDRG_MAX_MSG.  Of the
+ * usable entries that name message i the lowest (source, position) wins: a
+ * fill, a 64-bit atomicMin of the packed pair into an owner word per
+ * message, then a compare, as in xdrg_rpc_match_replies -- the outcome is a
+ * function of the inputs only.  *d_unused (may be NULL) = the entries that
+ * produced no reply, unusable or beaten by a lower entry; written by a
+ * kernel of the call (no memset, and no atomic on the one word).
+ *
+ * d_offsets[i] = the offset of message i's reply, d_offsets[n] = the total,
+ * also in d_status->total_bytes.  A capacity below the total is
+ * XDRG_ERR_OVERFLOW_PUT at the first message that does not fit (record = the
+ * message index, op 0xffff); every reply before it is written as in an
+ * unbounded call and nothing at or past out_capacity is written.  d_status
+ * is not initialised by the call (xdrg_status_init).
+ *
+ * Validated on the host before any HIP call.  XDRG_EINVAL: NULL d_offsets or
+ * d_status; NULL d_hdrs with n > 0; NULL srcs with nsrcs > 0; nsrcs >
+ * XDRG_RPC_MAX_RESULT_SRCS; a source with count_cap > 0 and NULL d_index,
+ * with d_bytes NULL and fixed_size != 0, or with d_bytes set, d_offsets NULL
+ * and fixed_size zero or not a multiple of 4.  XDRG_EALIGN: headers not
+ * 16-aligned, u64 arrays not 8-aligned, d_out or d_bytes not 4-aligned.
+ * XDRG_ESPACE: workspace below xdrg_rpc_reply_batch_workspace_size(n).
+ * n == 0: d_offsets[0] and the total are zeroed as xdrg_rpc_replies does, and
+ * *d_unused = the sum of the sources' counts.
+ *
+ * Kernels only: no memset node, no wait on the stream, no state; capturable
+ * into a graph on one stream.  `srcs` is a HOST array of device pointers:
+ * the sources travel as kernel arguments, as the plans of
+ * xdrg_rpc_verify_args do.
+ */
+typedef struct xdrg_rpc_result_src { /* 48 bytes */
+  const uint8_t *d_bytes;    /* xdr_to_opaque(r0, ..., r_count-1): xdrg_encode's output.  NULL: every result is void */
+  const uint64_t *d_offsets; /* count + 1 (xdrg_encode's d_offsets); NULL: result k = [k*fixed_size, (k+1)*fixed_size) */
+  const uint64_t *d_index;   /* count message numbers (xdrg_rpc_gather_args' d_index); any order */
+  const uint64_t *d_count;   /* device count (the gather's d_count); NULL: count_cap is the count */
+  uint64_t bytes_len;        /* bytes readable at d_bytes */
+  uint32_t count_cap;        /* host bound on the count (sizes the launch); min(*d_count, count_cap) entries are used */
+  uint32_t fixed_size;       /* used when d_offsets is NULL (0 with d_bytes NULL) */
+} xdrg_rpc_result_src;
+#define XDRG_RPC_MAX_RESULT_SRCS 64u
+
+size_t xdrg_rpc_reply_batch_workspace_size(uint64_t n);
+int xdrg_rpc_reply_batch(const xdrg_rpc_hdr *d_hdrs, uint64_t n,
+                         const xdrg_rpc_result_src *srcs /* HOST */, uint32_t nsrcs,
+                         void *d_out, uint64_t out_capacity, uint64_t *d_offsets /* n+1 */,
+                         uint64_t *d_unused /* may be NULL */,
+                         void *d_workspace, size_t workspace_bytes,
+                         xdrg_status *d_status, void *stream);
 
 /* Recursion depth per record: d_depths[i] = the deepest class/container
  * level record i's walk enters (the record itself is level 1), so

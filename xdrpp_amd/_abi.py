@@ -141,6 +141,7 @@ EXPORTED = (
     "xdrg_verify", "xdrg_rpc_verify_args", "xdrg_rpc_gather_args", "xdrg_rpc_gather_workspace_size",
     "xdrg_rpc_match_replies", "xdrg_rpc_verify_results", "xdrg_rpc_gather_results",
     "xdrg_rpc_gather_results_workspace_size",
+    "xdrg_rpc_reply_batch", "xdrg_rpc_reply_batch_workspace_size",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -168,6 +169,20 @@ class XdrgRpcArgplan(C.Structure):
 
 class XdrgRpcCall(C.Structure):
     _fields_ = [("xid", C.c_uint32), ("res", C.c_uint32)]
+
+
+RPC_MAX_RESULT_SRCS = 64  # XDRG_RPC_MAX_RESULT_SRCS
+
+
+class XdrgRpcResultSrc(C.Structure):
+    """xdrg_rpc_result_src: one source of results for xdrg_rpc_reply_batch
+    (a HOST record of device pointers)."""
+    _fields_ = [("d_bytes", C.c_void_p), ("d_offsets", C.c_void_p), ("d_index", C.c_void_p),
+                ("d_count", C.c_void_p), ("bytes_len", C.c_uint64), ("count_cap", C.c_uint32),
+                ("fixed_size", C.c_uint32)]
+
+
+assert C.sizeof(XdrgRpcResultSrc) == 48
 
 
 _lib = None
@@ -255,6 +270,10 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_gather_results.restype = C.c_int
     L.xdrg_rpc_gather_results_workspace_size.argtypes = [u64]
     L.xdrg_rpc_gather_results_workspace_size.restype = sz
+    L.xdrg_rpc_reply_batch.argtypes = [vp, u64, C.POINTER(XdrgRpcResultSrc), u32, vp, u64, vp, vp, vp, sz, vp, vp]
+    L.xdrg_rpc_reply_batch.restype = C.c_int
+    L.xdrg_rpc_reply_batch_workspace_size.argtypes = [u64]
+    L.xdrg_rpc_reply_batch_workspace_size.restype = sz
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

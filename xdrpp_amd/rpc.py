@@ -21,20 +21,26 @@ Host-side mirror of the reference's RPC message handling, batched:
       the reply that throws                                 -> verify_results(), gather_results(),
                                                                decode_results()
     xdr_to_msg(hdr, a...) of a call (arpc.h:44-59)          -> call_type() + Marshaler.encode_msgs
+    srpc_service::dispatch's reply (srpc.h:130-153), success
+      and error replies in the order srpc_server::run writes
+      them (srpc.cc:83-88)                                  -> reply_batch()
 
 Each header decodes to one 64-byte xdrg_rpc_hdr (HDR_DTYPE below).  The
 exceptions a client raises for a reply (xdr_call_error with the
 rpc_call_stat message, exception.h:25-57, rpc_msg.cc:8-109) come from
 raise_for_reply().  Every byte is produced by the HIP kernels of
-libxdrgpu.so (xdrpp_amd/csrc/rpc.hip, verify.hip, replies.hip).
+libxdrgpu.so (xdrpp_amd/csrc/rpc.hip, verify.hip, replies.hip,
+reply_batch.hip).
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _abi as A
-from .marshal import Marshaler, Plan, Status, XdrRuntimeError, _EXC, _ptr, _stream
+from .marshal import EncodeResult, Marshaler, Plan, Status, XdrRuntimeError, _EXC, _ptr, _stream
 from .xdr_types import Struct, UInt, XdrType
 
 HDR_DTYPE = np.dtype([("xid", "<u4"), ("action", "<u2"), ("err", "u1"), ("mtype", "u1"),
@@ -292,6 +298,108 @@ def decode_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tupl
         native, heap = Marshaler(plans[key], hdrs.device).decode(args, index.numel(), offs, stack_limit)
         out[key] = (index, native, heap)
     return out
+
+
+# ------------------------------------------------------ the reply stream
+@dataclass
+class ResultSource:
+    """One xdrg_rpc_result_src: the results of one Marshaler.encode and the
+    message each of them answers.  index: int64 [count] message numbers
+    (gather_args' index).  xdr: the encoded results, None for void results.
+    offsets: int64 [count + 1] (a var plan's EncodeResult.offsets), or None
+    with fixed_size = the plan's wire size.  count: an int64 [1] device tensor
+    read by the kernels (min(count, count_cap) entries are used), or None."""
+    index: torch.Tensor
+    xdr: torch.Tensor | None = None
+    offsets: torch.Tensor | None = None
+    fixed_size: int = 0
+    count: torch.Tensor | None = None
+    count_cap: int | None = None
+
+    @property
+    def cap(self) -> int:
+        return self.index.numel() if self.count_cap is None else self.count_cap
+
+
+def _result_srcs(sources) -> "C.Array":
+    if len(sources) > A.RPC_MAX_RESULT_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_RESULT_SRCS} result sources per call")
+    arr = (A.XdrgRpcResultSrc * max(len(sources), 1))()
+    for k, r in enumerate(sources):
+        if r.xdr is None or r.xdr.numel() == 0:  # no bytes: void results
+            if r.cap and r.fixed_size:
+                raise ValueError("reply_batch: fixed-size results without bytes")
+            arr[k] = A.XdrgRpcResultSrc(None, None, _ptr(r.index), _ptr(r.count), 0, r.cap, 0)
+            continue
+        arr[k] = A.XdrgRpcResultSrc(_ptr(r.xdr), _ptr(r.offsets), _ptr(r.index), _ptr(r.count),
+                                    r.xdr.numel(), r.cap, r.fixed_size)
+    return arr
+
+
+def launch_reply_batch(hdrs: torch.Tensor, sources: list[ResultSource], out: torch.Tensor, offsets: torch.Tensor,
+                       unused: torch.Tensor | None, status: Status, ws: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_reply_batch as it is: out uint8, offsets int64 [n + 1], unused
+    int64 [1] or None, ws uint8 of xdrg_rpc_reply_batch_workspace_size(n)
+    bytes.  `status` is not initialised here.  Kernels only: capturable."""
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    A.check(A.lib().xdrg_rpc_reply_batch(_ptr(hdrs), n, _result_srcs(sources), len(sources), _ptr(out), out.numel(),
+                                         _ptr(offsets), _ptr(unused), _ptr(ws), ws.numel(), status.ptr,
+                                         _stream() if stream is None else stream), "xdrg_rpc_reply_batch")
+
+
+def result_source(index: torch.Tensor, xdr=None, offsets_or_fixed_size=None) -> ResultSource:
+    """A ResultSource from (index, xdr, offsets_or_fixed_size): xdr None for
+    void results, a uint8 tensor, or what Marshaler.encode returned; the last
+    an int64 offsets tensor, the wire size of a fixed plan, or None (taken
+    from the EncodeResult; a fixed plan's size is then bytes / count)."""
+    if isinstance(xdr, EncodeResult):
+        if offsets_or_fixed_size is None:
+            offsets_or_fixed_size = xdr.offsets
+        xdr = xdr.xdr
+    if xdr is None:
+        return ResultSource(index)
+    if isinstance(offsets_or_fixed_size, torch.Tensor):
+        return ResultSource(index, xdr, offsets_or_fixed_size)
+    if offsets_or_fixed_size is None:
+        if index.numel() == 0 or xdr.numel() % index.numel():
+            raise ValueError("reply_batch: fixed-size results need their wire size")
+        offsets_or_fixed_size = xdr.numel() // index.numel()
+    return ResultSource(index, xdr, None, int(offsets_or_fixed_size))
+
+
+def reply_batch(hdrs: torch.Tensor, results: list, capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The replies of a dispatched batch whose handlers have run, as the one
+    stream srpc_server::run writes (srpc.cc:83-88): per message, in message
+    order, the success reply of the result that answers it, the error reply
+    of its header (error_replies()), or nothing (xdrg_rpc_reply_batch).
+    results: a list of (index, xdr, offsets_or_fixed_size) -- see
+    result_source() -- or ResultSource; at most 64: ValueError beyond.
+    Returns (stream, offsets int64 [n + 1]); reply i is
+    stream[offsets[i]:offsets[i + 1]].  One sync, for the total.  capacity:
+    bytes of the output (default 36 n + 28 entries + the result bytes, which
+    always holds them); a smaller one raises XdrRuntimeError
+    (XDRG_ERR_OVERFLOW_PUT) with record = the first message that does not
+    fit."""
+    srcs = [r if isinstance(r, ResultSource) else result_source(*r) for r in results]
+    if len(srcs) > A.RPC_MAX_RESULT_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_RESULT_SRCS} result sources per call")
+    dev = hdrs.device
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    L = A.lib()
+    cap = capacity
+    if cap is None:
+        cap = 36 * n + sum(28 * r.cap + (0 if r.xdr is None else r.xdr.numel()) for r in srcs)
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(L.xdrg_rpc_reply_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    launch_reply_batch(hdrs, srcs, out, offs, None, st, ws, s)
+    e = st.read(s)
+    if e.code:
+        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    return out[:int(e.total_bytes)], offs
 
 
 # ------------------------------------------------ the asynchronous client
