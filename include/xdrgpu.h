@@ -40,6 +40,10 @@
  *                                                            xdrpp/arpc.h:59-90
  *   xdrg_rpc_reply_batch  <- srpc_service::dispatch's reply, srpc.h:130-153; the
  *   (+ _workspace_size)      order srpc_server::run writes them in, srpc.cc:83-88
+ *   xdrg_rpc_next_xids    <- rpc_sock::get_xid               xdrpp/msgsock.h:118-122
+ *   xdrg_rpc_call_batch   <- xdr_to_msg(hdr, args...) of asynchronous_client_base::invoke
+ *   (+ _workspace_size)                                      xdrpp/arpc.h:41-59
+ *   xdrg_rpc_pending_add  <- rpc_sock::send_call: calls_     xdrpp/msgsock.cc:227-232
  *   xdrg_error_message   <- the what() strings of the exception types
  *                            xdrpp/types.h:57-99, marshal.h:104-108,152-170,
  *                            :131-136,:207-210, marshal.cc:43-57
@@ -76,6 +80,8 @@ extern "C" {
 
 #define XDRG_ABI_VERSION 10 /* 10: xdrg_rpc_match_replies, xdrg_rpc_verify_results, xdrg_rpc_gather_results;
                                    (additive, still 10) xdrg_rpc_reply_batch, xdrg_rpc_reply_batch_workspace_size;
+                                   (additive, still 10) xdrg_rpc_next_xids, xdrg_rpc_call_batch,
+                                   xdrg_rpc_call_batch_workspace_size, xdrg_rpc_pending_add;
                                9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
 
 /* ---------------------------------------------------------------------- */
@@ -1069,6 +1075,147 @@ int xdrg_rpc_reply_batch(const xdrg_rpc_hdr *d_hdrs, uint64_t n,
                          uint64_t *d_unused /* may be NULL */,
                          void *d_workspace, size_t workspace_bytes,
                          xdrg_status *d_status, void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* Client call batch                                                       */
+/* ---------------------------------------------------------------------- */
+/*
+ * asynchronous_client_base::invoke over rpc_sock (xdrpp/arpc.h:41-59,
+ * xdrpp/msgsock.h:118-122, xdrpp/msgsock.cc:227-232) takes an xid, marshals
+ * xdr_to_msg(hdr, args...) and remembers the call in calls_.  The three
+ * calls below do this for a batch whose calls go to many procedures: the
+ * xids, the one stream xdrg_index_msgs / xdrg_rpc_dispatch read on the
+ * server, and the pending table xdrg_rpc_match_replies searches.  All three
+ * validate on the host before any HIP call, launch kernels only (no memset
+ * node, no wait on the stream, no state; capturable on one stream) and
+ * neither read nor write anything outside the given arrays, whatever these
+ * hold.
+ */
+
+/*
+ * rpc_sock::get_xid() n times: d_xids[k] is what the (k+1)-th get_xid()
+ * returns when every earlier one was followed by send_call -- the (k+1)-th
+ * value after last_xid, counting upwards mod 2^32, that is not in the pending
+ * table d_calls (sorted as for xdrg_rpc_match_replies).  One lane per xid, no
+ * dependence between lanes: with r(x) = (x - last_xid - 1) mod 2^32 and the
+ * table read from lower_bound(last_xid + 1) on and around its end, R[0] <
+ * R[1] < ... are the pending values in the order get_xid meets them, and
+ * xid_k = last_xid + 1 + k + j for the smallest j with R[j] - j > k (64-bit
+ * arithmetic; j = ncalls when there is none).
+ *
+ * One departure from the reference: its loop `while (calls_.find(++xid_) !=
+ * calls_.end())` is written to stop at xid_ == 0 even when 0 is pending, and
+ * would hand out a duplicate.  Here a pending 0 is skipped like any other
+ * value.
+ *
+ * XDRG_EINVAL: ncalls + n > 0xffffffff (no n free values are left), NULL
+ * d_calls with ncalls > 0, NULL d_xids with n > 0.  XDRG_EALIGN: d_calls not
+ * 8-aligned, d_xids not 4-aligned.  n == 0: XDRG_OK, nothing launched.  An
+ * unsorted table gives unspecified xids.
+ */
+int xdrg_rpc_next_xids(const xdrg_rpc_call *d_calls, uint64_t ncalls, uint32_t last_xid,
+                       uint64_t n, uint32_t *d_xids /* n */, void *stream);
+
+/*
+ * The call stream.  The arguments come as up to XDRG_RPC_MAX_ARG_SRCS
+ * sources, each the output of one xdrg_encode for one procedure and the call
+ * position (0..n-1) every argument record belongs to.
+ *
+ * Call position i, in call order:
+ *   with a winning entry of L argument bytes
+ *                  the mark BE((40 + L) | XDRG_MARK_LAST), the ten words
+ *                  d_xids[i], CALL (0), 2, prog, vers, proc, 0, 0, 0, 0
+ *                  big-endian (cred and verf: AUTH_NONE opaque_auth with
+ *                  empty bodies, which is all invoke sends), then the L bytes
+ *                  verbatim: what xdrg_encode_msgs writes for the record
+ *                  "ten header words, then the arguments".  The argument
+ *                  bytes are not validated as XDR.
+ *   with no entry  no message: d_offsets[i] == d_offsets[i+1].
+ * d_sent[i] (may be NULL) = {d_xids[i], res of the winning source}, or
+ * {d_xids[i], XDRG_RPC_RES_UNSENT} for a position without a message: the
+ * d_new of xdrg_rpc_pending_add.
+ *
+ * Entry k of a source, k < min(*d_count, count_cap), names position
+ * d_index[k] and holds the bytes [d_offsets[k], d_offsets[k+1]) of d_bytes
+ * (d_offsets NULL: [k * fixed_size, (k+1) * fixed_size); d_bytes NULL: no
+ * bytes, and d_offsets is not read).  An entry is not usable, and nothing of
+ * d_bytes is read for it, when index >= n, when its span has end < begin or
+ * end > bytes_len, when its offset or length is not a multiple of 4, or when
+ * 40 + L > XDRG_MAX_MSG.  Of the usable entries that name position i the
+ * lowest (source, position) wins: a fill, a 64-bit atomicMin of the packed
+ * pair into an owner word per position, then a compare -- the outcome is a
+ * function of the inputs only.  d_counts (may be NULL): d_counts[0] = the
+ * positions without a message, d_counts[1] = the entries that produced none,
+ * unusable or beaten by a lower entry; both written by a kernel of the call
+ * from tile sums (no memset, and no atomic on the one word).
+ *
+ * d_offsets[i] = the offset of position i's message, d_offsets[n] = the
+ * total, also in d_status->total_bytes.  A capacity below the total is
+ * XDRG_ERR_OVERFLOW_PUT at the first position that does not fit (record = the
+ * position, op 0xffff); every message before it is written as in an unbounded
+ * call and nothing at or past out_capacity is written.  d_status is not
+ * initialised by the call (xdrg_status_init).
+ *
+ * XDRG_EINVAL: NULL d_offsets or d_status; NULL d_xids with n > 0; NULL srcs
+ * with nsrcs > 0; nsrcs > XDRG_RPC_MAX_ARG_SRCS; a source with count_cap > 0
+ * and NULL d_index, with d_bytes NULL and fixed_size != 0, or with d_bytes
+ * set, d_offsets NULL and fixed_size zero or not a multiple of 4; NULL d_out
+ * with a capacity.  XDRG_EALIGN: u64 arrays, d_sent or d_counts not
+ * 8-aligned, d_xids, d_out or d_bytes not 4-aligned.  XDRG_ESPACE: workspace
+ * below xdrg_rpc_call_batch_workspace_size(n).  n == 0: d_offsets[0] and the
+ * total are zeroed, d_counts = {0, the sum of the sources' counts}.
+ *
+ * `srcs` is a HOST array of device pointers: the sources travel as kernel
+ * arguments, as those of xdrg_rpc_reply_batch do.
+ */
+typedef struct xdrg_rpc_arg_src { /* 64 bytes */
+  const uint8_t *d_bytes;    /* xdrg_encode's output for this procedure's arguments.  NULL: no arguments */
+  const uint64_t *d_offsets; /* count + 1 (xdrg_encode's d_offsets); NULL: entry k = [k*fixed_size, (k+1)*fixed_size) */
+  const uint64_t *d_index;   /* count call positions (0..n-1); any order */
+  const uint64_t *d_count;   /* device count; NULL: count_cap is the count */
+  uint64_t bytes_len;        /* bytes readable at d_bytes */
+  uint32_t count_cap;        /* host bound on the count (sizes the launch); min(*d_count, count_cap) entries are used */
+  uint32_t fixed_size;       /* used when d_offsets is NULL (0 with d_bytes NULL) */
+  uint32_t prog, vers, proc; /* P::interface_type::program / version, P::proc (arpc.h:46-48) */
+  uint32_t res;              /* the procedure's result type number, for the pending table */
+} xdrg_rpc_arg_src;
+#define XDRG_RPC_MAX_ARG_SRCS 64u
+#define XDRG_RPC_RES_UNSENT 0xffffffffu
+
+size_t xdrg_rpc_call_batch_workspace_size(uint64_t n);
+int xdrg_rpc_call_batch(const uint32_t *d_xids, uint64_t n,
+                        const xdrg_rpc_arg_src *srcs /* HOST */, uint32_t nsrcs,
+                        void *d_out, uint64_t out_capacity, uint64_t *d_offsets /* n+1 */,
+                        xdrg_rpc_call *d_sent /* n, call order; may be NULL */,
+                        uint64_t *d_counts /* 2, may be NULL */,
+                        void *d_workspace, size_t workspace_bytes, xdrg_status *d_status, void *stream);
+
+/*
+ * rpc_sock::calls_ after the sends: d_merged = the sorted table d_calls
+ * merged with d_new, where d_new is xdrg_rpc_call_batch's d_sent over
+ * xdrg_rpc_next_xids' xids -- ascending as unsigned except for at most one
+ * descent (the wrap past 2^32 - 1), and disjoint from the table.  New entry k
+ * lands at lower_bound(table, xid_k) plus the new entries with a smaller
+ * xid: (n - w) + k before the wrap point w, k - w from it on (w by a binary
+ * search over d_new); old entry j lands at j plus the new entries below it.
+ * d_old_pos[j] / d_new_pos[k] (may be NULL) = where old entry j / new entry k
+ * went.
+ *
+ * EVERY entry of d_new is merged, XDRG_RPC_RES_UNSENT ones included: a caller
+ * that leaves calls unsent filters them first.  A d_new or a table that
+ * breaks the precondition gives an unspecified table, but every write stays
+ * inside d_merged and the two position arrays.
+ *
+ * XDRG_EINVAL: NULL d_calls with ncalls > 0, NULL d_new with n > 0, NULL
+ * d_merged with ncalls + n > 0; d_merged equal to or overlapping d_calls or
+ * d_new.  XDRG_EALIGN: any array not 8-aligned.  ncalls + n == 0: XDRG_OK,
+ * nothing launched.
+ */
+int xdrg_rpc_pending_add(const xdrg_rpc_call *d_calls, uint64_t ncalls,
+                         const xdrg_rpc_call *d_new /* n */, uint64_t n,
+                         xdrg_rpc_call *d_merged /* ncalls + n */,
+                         uint64_t *d_old_pos /* ncalls, may be NULL */,
+                         uint64_t *d_new_pos /* n, may be NULL */, void *stream);
 
 /* Recursion depth per record: d_depths[i] = the deepest class/container
  * level record i's walk enters (the record itself is level 1), so

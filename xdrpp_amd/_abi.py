@@ -142,6 +142,7 @@ EXPORTED = (
     "xdrg_rpc_match_replies", "xdrg_rpc_verify_results", "xdrg_rpc_gather_results",
     "xdrg_rpc_gather_results_workspace_size",
     "xdrg_rpc_reply_batch", "xdrg_rpc_reply_batch_workspace_size",
+    "xdrg_rpc_next_xids", "xdrg_rpc_call_batch", "xdrg_rpc_call_batch_workspace_size", "xdrg_rpc_pending_add",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -183,6 +184,21 @@ class XdrgRpcResultSrc(C.Structure):
 
 
 assert C.sizeof(XdrgRpcResultSrc) == 48
+
+RPC_MAX_ARG_SRCS = 64        # XDRG_RPC_MAX_ARG_SRCS
+RPC_RES_UNSENT = 0xFFFFFFFF  # XDRG_RPC_RES_UNSENT
+
+
+class XdrgRpcArgSrc(C.Structure):
+    """xdrg_rpc_arg_src: one procedure's arguments for xdrg_rpc_call_batch
+    (a HOST record of device pointers)."""
+    _fields_ = [("d_bytes", C.c_void_p), ("d_offsets", C.c_void_p), ("d_index", C.c_void_p),
+                ("d_count", C.c_void_p), ("bytes_len", C.c_uint64), ("count_cap", C.c_uint32),
+                ("fixed_size", C.c_uint32), ("prog", C.c_uint32), ("vers", C.c_uint32), ("proc", C.c_uint32),
+                ("res", C.c_uint32)]
+
+
+assert C.sizeof(XdrgRpcArgSrc) == 64
 
 
 _lib = None
@@ -274,6 +290,14 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_reply_batch.restype = C.c_int
     L.xdrg_rpc_reply_batch_workspace_size.argtypes = [u64]
     L.xdrg_rpc_reply_batch_workspace_size.restype = sz
+    L.xdrg_rpc_next_xids.argtypes = [vp, u64, u32, u64, vp, vp]
+    L.xdrg_rpc_next_xids.restype = C.c_int
+    L.xdrg_rpc_call_batch.argtypes = [vp, u64, C.POINTER(XdrgRpcArgSrc), u32, vp, u64, vp, vp, vp, vp, sz, vp, vp]
+    L.xdrg_rpc_call_batch.restype = C.c_int
+    L.xdrg_rpc_call_batch_workspace_size.argtypes = [u64]
+    L.xdrg_rpc_call_batch_workspace_size.restype = sz
+    L.xdrg_rpc_pending_add.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp]
+    L.xdrg_rpc_pending_add.restype = C.c_int
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

@@ -21,6 +21,11 @@ Host-side mirror of the reference's RPC message handling, batched:
       the reply that throws                                 -> verify_results(), gather_results(),
                                                                decode_results()
     xdr_to_msg(hdr, a...) of a call (arpc.h:44-59)          -> call_type() + Marshaler.encode_msgs
+    asynchronous_client_base::invoke for a batch of calls
+      to many procedures (arpc.h:41-59): rpc_sock::get_xid
+      (msgsock.h:118-122), xdr_to_msg(hdr, args...), and
+      calls_ after send_call (msgsock.cc:227-232)           -> call_batch() (launch_next_xids,
+                                                               launch_call_batch, launch_pending_add)
     srpc_service::dispatch's reply (srpc.h:130-153), success
       and error replies in the order srpc_server::run writes
       them (srpc.cc:83-88)                                  -> reply_batch()
@@ -30,7 +35,7 @@ exceptions a client raises for a reply (xdr_call_error with the
 rpc_call_stat message, exception.h:25-57, rpc_msg.cc:8-109) come from
 raise_for_reply().  Every byte is produced by the HIP kernels of
 libxdrgpu.so (xdrpp_amd/csrc/rpc.hip, verify.hip, replies.hip,
-reply_batch.hip).
+reply_batch.hip, call_batch.hip).
 """
 from __future__ import annotations
 
@@ -426,9 +431,10 @@ class PendingCalls:
     unsigned (the table xdrg_rpc_match_replies searches), raises ValueError on
     a duplicate xid, and keeps the device table and the permutation, so that
     everything the functions below take and return names a call by its
-    position in `xids`."""
+    position in `xids`.  last_xid: rpc_sock::xid_, the last xid handed out (0
+    in a fresh rpc_sock); call_batch() counts on from it."""
 
-    def __init__(self, xids, res, device="cuda"):
+    def __init__(self, xids, res, device="cuda", *, last_xid: int = 0):
         if isinstance(xids, torch.Tensor):
             xids = xids.cpu().numpy()
         if isinstance(res, torch.Tensor):
@@ -445,10 +451,36 @@ class PendingCalls:
         inv[order] = np.arange(x.size, dtype=np.int64)
         self.device = torch.device(device)
         self.ncalls = int(x.size)
-        self.calls = t                                                  # host copy, sorted
+        self.last_xid = int(last_xid) & 0xFFFFFFFF
+        self._calls = t                                                 # host copy, sorted
         self.table = torch.from_numpy(t.view(np.int64).copy()).to(self.device)  # xdrg_rpc_call [ncalls]
         self.perm = torch.from_numpy(order.astype(np.int64)).to(self.device)    # table position -> caller's
         self.inv = torch.from_numpy(inv).to(self.device)                        # caller's -> table position
+
+    @classmethod
+    def from_device(cls, table: torch.Tensor, inv: torch.Tensor, *, last_xid: int = 0) -> "PendingCalls":
+        """A table that is on the device already, without a host sort: `table`
+        int64 [ncalls], xdrg_rpc_call records sorted by xid as unsigned with
+        no duplicates (xdrg_rpc_pending_add's d_merged; not checked), `inv`
+        int64 [ncalls], the table position of the caller's call c (its
+        d_old_pos / d_new_pos)."""
+        self = cls.__new__(cls)
+        self.device = table.device
+        self.ncalls = int(table.numel())
+        self.last_xid = int(last_xid) & 0xFFFFFFFF
+        self._calls = None
+        self.table, self.inv = table, inv
+        self.perm = torch.empty_like(inv)
+        self.perm[inv] = torch.arange(self.ncalls, dtype=torch.int64, device=self.device)
+        return self
+
+    @property
+    def calls(self) -> np.ndarray:
+        """The sorted table on the host (a device-built one is copied at the
+        first use)."""
+        if self._calls is None:
+            self._calls = self.table.cpu().numpy().view(CALL_DTYPE).reshape(-1).copy()
+        return self._calls
 
     def to_caller(self, call: torch.Tensor) -> torch.Tensor:
         """d_call (table positions, -1 for none) in the caller's positions."""
@@ -460,6 +492,159 @@ class PendingCalls:
         if self.ncalls == 0:
             return call
         return torch.where(call >= 0, self.inv[call.clamp(min=0)], call)
+
+
+# ------------------------------------------------ the client's call stream
+@dataclass
+class ArgSource:
+    """One xdrg_rpc_arg_src: the arguments of one procedure's calls, as one
+    Marshaler.encode wrote them, and the call position of each.  key: (prog,
+    vers, proc).  res: the number of the procedure's result type (what
+    PendingCalls keeps per call).  index: int64 [count] call positions.  xdr:
+    the encoded arguments, None for a procedure without arguments.  offsets:
+    int64 [count + 1] (a var plan's EncodeResult.offsets), or None with
+    fixed_size = the plan's wire size.  count: an int64 [1] device tensor read
+    by the kernels (min(count, count_cap) entries are used), or None."""
+    key: tuple[int, int, int]
+    res: int
+    index: torch.Tensor
+    xdr: torch.Tensor | None = None
+    offsets: torch.Tensor | None = None
+    fixed_size: int = 0
+    count: torch.Tensor | None = None
+    count_cap: int | None = None
+
+    @property
+    def cap(self) -> int:
+        return self.index.numel() if self.count_cap is None else self.count_cap
+
+
+def arg_source(key, res: int, index: torch.Tensor, xdr=None, offsets_or_fixed_size=None) -> ArgSource:
+    """An ArgSource from (key, res, index, xdr, offsets_or_fixed_size): xdr
+    None for a procedure without arguments, a uint8 tensor, or what
+    Marshaler.encode returned; the last an int64 offsets tensor, the wire size
+    of a fixed plan, or None (taken from the EncodeResult; a fixed plan's size
+    is then bytes / count)."""
+    key = tuple(int(v) for v in key)
+    if isinstance(xdr, EncodeResult):
+        if offsets_or_fixed_size is None:
+            offsets_or_fixed_size = xdr.offsets
+        xdr = xdr.xdr
+    if xdr is None:
+        return ArgSource(key, int(res), index)
+    if isinstance(offsets_or_fixed_size, torch.Tensor):
+        return ArgSource(key, int(res), index, xdr, offsets_or_fixed_size)
+    if offsets_or_fixed_size is None:
+        if index.numel() == 0 or xdr.numel() % index.numel():
+            raise ValueError("call_batch: fixed-size arguments need their wire size")
+        offsets_or_fixed_size = xdr.numel() // index.numel()
+    return ArgSource(key, int(res), index, xdr, None, int(offsets_or_fixed_size))
+
+
+def _arg_srcs(sources) -> "C.Array":
+    if len(sources) > A.RPC_MAX_ARG_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_ARG_SRCS} argument sources per call")
+    arr = (A.XdrgRpcArgSrc * max(len(sources), 1))()
+    for k, r in enumerate(sources):
+        prog, vers, proc = r.key
+        if r.xdr is None or r.xdr.numel() == 0:  # no bytes: a procedure without arguments
+            if r.cap and r.fixed_size:
+                raise ValueError("call_batch: fixed-size arguments without bytes")
+            arr[k] = A.XdrgRpcArgSrc(None, None, _ptr(r.index), _ptr(r.count), 0, r.cap, 0, prog, vers, proc, r.res)
+            continue
+        arr[k] = A.XdrgRpcArgSrc(_ptr(r.xdr), _ptr(r.offsets), _ptr(r.index), _ptr(r.count), r.xdr.numel(), r.cap,
+                                 r.fixed_size, prog, vers, proc, r.res)
+    return arr
+
+
+def launch_next_xids(pending: PendingCalls, xids: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_next_xids as it is: xids int32 [n] takes the next n xids after
+    pending.last_xid that are not in pending.table.  Kernels only:
+    capturable."""
+    A.check(A.lib().xdrg_rpc_next_xids(_ptr(pending.table), pending.ncalls, pending.last_xid, xids.numel(),
+                                       _ptr(xids), _stream() if stream is None else stream), "xdrg_rpc_next_xids")
+
+
+def launch_call_batch(xids: torch.Tensor, sources: list[ArgSource], out: torch.Tensor, offsets: torch.Tensor,
+                      sent: torch.Tensor | None, counts: torch.Tensor | None, status: Status, ws: torch.Tensor,
+                      stream=None) -> None:
+    """xdrg_rpc_call_batch as it is: xids int32 [n], out uint8, offsets int64
+    [n + 1], sent int64 [n] (xdrg_rpc_call records) or None, counts int64 [2]
+    or None, ws uint8 of xdrg_rpc_call_batch_workspace_size(n) bytes.
+    `status` is not initialised here.  Kernels only: capturable."""
+    A.check(A.lib().xdrg_rpc_call_batch(_ptr(xids), xids.numel(), _arg_srcs(sources), len(sources), _ptr(out),
+                                        out.numel(), _ptr(offsets), _ptr(sent), _ptr(counts), _ptr(ws), ws.numel(),
+                                        status.ptr, _stream() if stream is None else stream), "xdrg_rpc_call_batch")
+
+
+def launch_pending_add(pending: PendingCalls, new: torch.Tensor, merged: torch.Tensor,
+                       old_pos: torch.Tensor | None, new_pos: torch.Tensor | None, stream=None) -> None:
+    """xdrg_rpc_pending_add as it is: new int64 [n] (launch_call_batch's
+    sent; every entry is merged, XDRG_RPC_RES_UNSENT ones too), merged int64
+    [ncalls + n], old_pos int64 [ncalls] and new_pos int64 [n] in TABLE
+    positions, or None.  Kernels only: capturable."""
+    A.check(A.lib().xdrg_rpc_pending_add(_ptr(pending.table), pending.ncalls, _ptr(new), new.numel(), _ptr(merged),
+                                         _ptr(old_pos), _ptr(new_pos), _stream() if stream is None else stream),
+            "xdrg_rpc_pending_add")
+
+
+def call_batch(pending: PendingCalls, sources: list, n: int | None = None,
+               capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, PendingCalls]:
+    """asynchronous_client_base::invoke (arpc.h:41-59) for a batch of n calls
+    to many procedures: the next n xids after pending.last_xid that are not
+    pending (rpc_sock::get_xid), the calls as the one record-marked stream the
+    socket would carry, in call order (xdrg_rpc_call_batch), and calls_ after
+    the sends (xdrg_rpc_pending_add), all on the device.
+    sources: a list of (key, res, index, xdr, offsets_or_fixed_size) -- see
+    arg_source() -- or ArgSource, one per procedure; at most 64: ValueError
+    beyond.  n: the calls (default: the sources' entries).  Every call
+    position 0..n-1 must be named by exactly one usable entry: ValueError for
+    a position left unsent or an entry left unused.  Returns (stream, offsets
+    int64 [n + 1], xids int32 [n], pending2): call i is
+    stream[offsets[i]:offsets[i + 1]] with xid xids[i].  In pending2 the old
+    calls keep their caller positions 0..ncalls-1 and call i is ncalls + i; it
+    equals PendingCalls(old xids + xids, old res + the sources' res), built
+    without a host sort, and its last_xid is the last xid issued.  One sync,
+    for the total and the counts.  capacity: bytes of the output (default 44 n
+    + the argument bytes, which always holds them); a smaller one raises
+    XdrRuntimeError (XDRG_ERR_OVERFLOW_PUT) with record = the first call that
+    does not fit."""
+    srcs = [r if isinstance(r, ArgSource) else arg_source(*r) for r in sources]
+    if len(srcs) > A.RPC_MAX_ARG_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_ARG_SRCS} argument sources per call")
+    dev = pending.device
+    if n is None:
+        n = sum(r.cap for r in srcs)
+    L = A.lib()
+    cap = capacity
+    if cap is None:
+        cap = 44 * n + sum(0 if r.xdr is None else r.xdr.numel() for r in srcs)
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    xids = torch.empty(n, dtype=torch.int32, device=dev)
+    sent = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    merged = torch.empty(pending.ncalls + n, dtype=torch.int64, device=dev)
+    pos = torch.empty(pending.ncalls + n, dtype=torch.int64, device=dev)  # old_pos, then new_pos
+    ws = torch.empty(max(L.xdrg_rpc_call_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    launch_next_xids(pending, xids, s)
+    launch_call_batch(xids, srcs, out, offs, sent, counts, st, ws, s)
+    launch_pending_add(pending, sent, merged, pos[:pending.ncalls], pos[pending.ncalls:], s)
+    e = st.read(s)  # the one sync; what follows is ready
+    unsent, unused = counts.tolist()
+    if unsent or unused:
+        raise ValueError(f"call_batch: {unsent} call positions without a usable entry, {unused} entries unused")
+    if e.code:
+        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    last = int(xids[-1].item()) & 0xFFFFFFFF if n else pending.last_xid
+    # the caller's call c sits where its old table position went; call i where new entry i went
+    old_pos, new_pos = pos[:pending.ncalls], pos[pending.ncalls:]
+    inv = torch.cat([old_pos[pending.inv], new_pos])
+    pending2 = PendingCalls.from_device(merged, inv, last_xid=last)
+    return out[:int(e.total_bytes)], offs, xids, pending2
 
 
 def launch_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, pending: PendingCalls,
