@@ -36,6 +36,11 @@
  *                                                            srpc.h:130-134
  *   xdrg_rpc_match_replies <- rpc_sock::recv_msg: xid -> pending call
  *                                                            xdrpp/msgsock.cc:202-232
+ *   xdrg_rpc_call_stats   <- rpc_call_stat(hdr), the call_result of invoke's callback
+ *                                                            xdrpp/rpc_msg.cc:69-90,
+ *                                                            exception.h:28-51, arpc.h:60-61
+ *   xdrg_rpc_pending_retire <- recv_msg's calls_.erase, abort_all_calls
+ *   (+ _workspace_size)                                      xdrpp/msgsock.cc:217-219,:190-200
  *   xdrg_rpc_verify_results <- the reply callback of asynchronous_client_base::invoke
  *                                                            xdrpp/arpc.h:59-90
  *   xdrg_rpc_reply_batch  <- srpc_service::dispatch's reply, srpc.h:130-153; the
@@ -82,6 +87,8 @@ extern "C" {
                                    (additive, still 10) xdrg_rpc_reply_batch, xdrg_rpc_reply_batch_workspace_size;
                                    (additive, still 10) xdrg_rpc_next_xids, xdrg_rpc_call_batch,
                                    xdrg_rpc_call_batch_workspace_size, xdrg_rpc_pending_add;
+                                   (additive, still 10) xdrg_rpc_call_stats, xdrg_rpc_pending_retire,
+                                   xdrg_rpc_pending_retire_workspace_size;
                                9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
 
 /* ---------------------------------------------------------------------- */
@@ -1216,6 +1223,103 @@ int xdrg_rpc_pending_add(const xdrg_rpc_call *d_calls, uint64_t ncalls,
                          xdrg_rpc_call *d_merged /* ncalls + n */,
                          uint64_t *d_old_pos /* ncalls, may be NULL */,
                          uint64_t *d_new_pos /* n, may be NULL */, void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* Settling a reply batch                                                  */
+/* ---------------------------------------------------------------------- */
+/*
+ * rpc_sock does three things with calls_: send_call emplaces the call
+ * (xdrpp/msgsock.cc:227-232; xdrg_rpc_pending_add), recv_msg erases it at its
+ * first reply, before the callback runs (msgsock.cc:217-219), and
+ * abort_all_calls empties calls_ and hands every callback nullptr
+ * (msgsock.cc:190-200), which invoke's lambda turns into
+ * rpc_call_stat::NETWORK_ERROR (xdrpp/arpc.h:60-61).  The callback receives a
+ * call_result per call, which is an rpc_call_stat (xdrpp/exception.h:28-51)
+ * built by rpc_call_stat(hdr) (xdrpp/rpc_msg.cc:69-90).  The two calls below
+ * give, after a reply batch, every pending call's rpc_call_stat in one device
+ * array and the table that goes into the next round: calls_ as the reference
+ * would hold it.  Over that table xdrg_rpc_match_replies reports a late
+ * duplicate of a retired call as XDRG_RPCR_UNKNOWN_XID (msgsock.cc:212-216)
+ * and xdrg_rpc_next_xids skips only what is pending now (msgsock.h:118-122).
+ *
+ * Both validate on the host before any HIP call, launch kernels only (no
+ * memset or memcpy node, no wait on the stream, no state; capturable on one
+ * stream), use no atomic -- the result is a function of the inputs only --
+ * and neither read nor write anything outside the given arrays, whatever
+ * these hold.
+ */
+typedef struct xdrg_rpc_call_stat { uint32_t type; uint32_t stat; } xdrg_rpc_call_stat; /* 8 bytes */
+/* type: rpc_call_stat::stat_type in the reference's order (exception.h:29-36) */
+#define XDRG_RPCS_ACCEPT_STAT 0u      /* stat = accept_stat; {0, 0} is success (operator bool, exception.h:48-50) */
+#define XDRG_RPCS_AUTH_STAT 1u        /* stat = auth_stat (rj_why) */
+#define XDRG_RPCS_RPCVERS_MISMATCH 2u /* stat = 0 */
+#define XDRG_RPCS_GARBAGE_RES 3u      /* stat = 0 */
+#define XDRG_RPCS_NETWORK_ERROR 4u    /* stat = 0 */
+#define XDRG_RPCS_BAD_ALLOC 5u        /* named for completeness; never produced */
+#define XDRG_RPCS_PENDING 0xffffffffu /* not a reference value: no reply yet */
+
+/*
+ * What cb receives for every pending call.  One lane per table entry c;
+ * d_hdrs holds the batch's headers after xdrg_rpc_verify_results, d_reply_of
+ * what xdrg_rpc_match_replies wrote.  With i = d_reply_of[c]:
+ *   i == XDRG_RPC_NO_CALL  {unanswered, 0}.  unanswered is XDRG_RPCS_PENDING
+ *                          (a reply batch in normal operation) or
+ *                          XDRG_RPCS_NETWORK_ERROR (the caller runs
+ *                          abort_all_calls: every call still outstanding
+ *                          gets cb(NETWORK_ERROR))
+ *   i < n                  by d_hdrs[i].action, as rpc_call_stat(hdr) and the
+ *                          catch of arpc.h:87-89 give it:
+ *     XDRG_RPCR_OK                {ACCEPT_STAT, 0}
+ *     XDRG_RPCR_ACCEPT_STAT       {ACCEPT_STAT, w[XDRG_RPC_W_STAT]}
+ *     XDRG_RPCR_AUTH_STAT         {AUTH_STAT, w[XDRG_RPC_W_WHY]}
+ *     XDRG_RPCR_RPCVERS_MISMATCH  {RPCVERS_MISMATCH, 0}
+ *     anything else               {GARBAGE_RES, 0}: GARBAGE_RES, MALFORMED,
+ *                                 NOT_REPLY and any action a matched reply
+ *                                 cannot carry
+ *   any other i            (at or past n: no message of this batch)
+ *                          {GARBAGE_RES, 0}; no header is read
+ * XDRG_EINVAL: unanswered neither of the two values; with ncalls > 0, NULL
+ * d_reply_of or d_stats, or NULL d_hdrs with n > 0.  XDRG_EALIGN: d_hdrs not
+ * 16-aligned, d_reply_of or d_stats not 8-aligned.  XDRG_EUNSUPPORTED: more
+ * than 0x7fffffff workgroups.  ncalls == 0: XDRG_OK, nothing launched.
+ * Nothing of d_hdrs is written, and nothing of it is read for a call without
+ * a reply in this batch.
+ */
+int xdrg_rpc_call_stats(const xdrg_rpc_hdr *d_hdrs, uint64_t n,
+                        const uint64_t *d_reply_of /* ncalls, table order */, uint64_t ncalls,
+                        uint32_t unanswered, xdrg_rpc_call_stat *d_stats /* ncalls */, void *stream);
+
+/*
+ * calls_ after the erases of a reply batch.  Entry j of the sorted table is
+ * kept iff d_reply_of[j] == XDRG_RPC_NO_CALL; any other value means the entry
+ * was answered, whatever the value is (as in xdrg_rpc_call_stats).  The kept
+ * entries go to d_kept[0..count) in table order, so d_kept is again sorted
+ * with no duplicates; *d_count = count; d_kept_pos[j] (may be NULL) = the new
+ * table position of old entry j, or XDRG_RPC_NO_CALL when it was retired.
+ * Entries of d_kept at or past count are unspecified; nothing at or past
+ * d_kept + ncalls is written, and nothing of d_calls or d_reply_of is.
+ *
+ * An ordered stream compaction in three passes: the kept entries of every
+ * 256-entry tile; the exclusive scan of the tile counts in one workgroup,
+ * which also writes *d_count; a scatter in which a lane's rank is the kept
+ * lanes below it in its wave's 64-bit ballot, plus the waves before it in the
+ * tile, plus the tile's base.  No atomic counter (the order is the table's).
+ * The workspace holds the tile counts only and need not be initialised.
+ *
+ * XDRG_EINVAL: NULL d_count; with ncalls > 0, NULL d_calls, d_reply_of or
+ * d_kept, or d_kept equal to or overlapping d_calls (an in-place compaction
+ * would race between workgroups).  XDRG_EALIGN: any array not 8-aligned.
+ * XDRG_ESPACE: workspace below xdrg_rpc_pending_retire_workspace_size(ncalls).
+ * XDRG_EUNSUPPORTED: more than 0x7fffffff workgroups.  ncalls == 0: *d_count =
+ * 0 is still written, by a kernel; no workspace is needed.
+ */
+size_t xdrg_rpc_pending_retire_workspace_size(uint64_t ncalls);
+int xdrg_rpc_pending_retire(const xdrg_rpc_call *d_calls, uint64_t ncalls,
+                            const uint64_t *d_reply_of /* ncalls */,
+                            xdrg_rpc_call *d_kept /* ncalls entries of room */,
+                            uint64_t *d_kept_pos /* ncalls, may be NULL */,
+                            uint64_t *d_count /* device u64 */,
+                            void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Recursion depth per record: d_depths[i] = the deepest class/container
  * level record i's walk enters (the record itself is level 1), so

@@ -10,6 +10,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libxdrgpu.so")
 
 # enum xdrg_op_kind
@@ -143,6 +145,7 @@ EXPORTED = (
     "xdrg_rpc_gather_results_workspace_size",
     "xdrg_rpc_reply_batch", "xdrg_rpc_reply_batch_workspace_size",
     "xdrg_rpc_next_xids", "xdrg_rpc_call_batch", "xdrg_rpc_call_batch_workspace_size", "xdrg_rpc_pending_add",
+    "xdrg_rpc_call_stats", "xdrg_rpc_pending_retire", "xdrg_rpc_pending_retire_workspace_size",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -199,6 +202,14 @@ class XdrgRpcArgSrc(C.Structure):
 
 
 assert C.sizeof(XdrgRpcArgSrc) == 64
+
+# xdrg_rpc_call_stat.type: rpc_call_stat::stat_type (exception.h:29-36), and PENDING for no reply yet
+RPCS_ACCEPT_STAT, RPCS_AUTH_STAT, RPCS_RPCVERS_MISMATCH, RPCS_GARBAGE_RES, RPCS_NETWORK_ERROR, \
+    RPCS_BAD_ALLOC = range(6)
+RPCS_PENDING = 0xFFFFFFFF    # XDRG_RPCS_PENDING
+RPC_CALL_STAT_BYTES = 8      # sizeof(xdrg_rpc_call_stat)
+CALL_STAT_DTYPE = np.dtype([("type", "<u4"), ("stat", "<u4")])
+assert CALL_STAT_DTYPE.itemsize == RPC_CALL_STAT_BYTES
 
 
 _lib = None
@@ -298,6 +309,12 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_call_batch_workspace_size.restype = sz
     L.xdrg_rpc_pending_add.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp]
     L.xdrg_rpc_pending_add.restype = C.c_int
+    L.xdrg_rpc_call_stats.argtypes = [vp, u64, vp, u64, u32, vp, vp]
+    L.xdrg_rpc_call_stats.restype = C.c_int
+    L.xdrg_rpc_pending_retire_workspace_size.argtypes = [u64]
+    L.xdrg_rpc_pending_retire_workspace_size.restype = sz
+    L.xdrg_rpc_pending_retire.argtypes = [vp, u64, vp, vp, vp, vp, vp, sz, vp]
+    L.xdrg_rpc_pending_retire.restype = C.c_int
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

@@ -29,13 +29,18 @@ Host-side mirror of the reference's RPC message handling, batched:
     srpc_service::dispatch's reply (srpc.h:130-153), success
       and error replies in the order srpc_server::run writes
       them (srpc.cc:83-88)                                  -> reply_batch()
+    the call_result of invoke's callback, rpc_call_stat(hdr)
+      (rpc_msg.cc:69-90), recv_msg's calls_.erase at the
+      first reply (msgsock.cc:217-219) and abort_all_calls
+      (msgsock.cc:190-200, arpc.h:60-61)                    -> call_stats(), PendingCalls.retire(),
+                                                               settle()
 
 Each header decodes to one 64-byte xdrg_rpc_hdr (HDR_DTYPE below).  The
 exceptions a client raises for a reply (xdr_call_error with the
 rpc_call_stat message, exception.h:25-57, rpc_msg.cc:8-109) come from
 raise_for_reply().  Every byte is produced by the HIP kernels of
 libxdrgpu.so (xdrpp_amd/csrc/rpc.hip, verify.hip, replies.hip,
-reply_batch.hip, call_batch.hip).
+reply_batch.hip, call_batch.hip, settle.hip).
 """
 from __future__ import annotations
 
@@ -493,6 +498,38 @@ class PendingCalls:
             return call
         return torch.where(call >= 0, self.inv[call.clamp(min=0)], call)
 
+    def retire(self, reply_of: torch.Tensor) -> tuple["PendingCalls", torch.Tensor]:
+        """calls_ after the erases of a reply batch (recv_msg, msgsock.cc:
+        217-219; xdrg_rpc_pending_retire).  reply_of: match_replies()'s, in
+        the caller's positions; a call is retired iff its entry is not -1.
+        Returns (pending2, old_of_new): the surviving calls renumbered
+        0..count-1 in ascending old caller position, old_of_new int64 [count]
+        = the old caller position of call p of pending2.  pending2 equals
+        PendingCalls(the survivors' xids in that order, their res,
+        last_xid=self.last_xid) (erasing a call does not touch xid_), built
+        without a host sort or a host copy of the table.  One sync, for the
+        count."""
+        dev, nc = self.device, self.ncalls
+        if nc == 0:
+            e = torch.empty(0, dtype=torch.int64, device=dev)
+            return PendingCalls.from_device(e, e.clone(), last_xid=self.last_xid), e.clone()
+        treply = torch.empty_like(reply_of)
+        treply[self.inv] = reply_of
+        kept = torch.empty(nc, dtype=torch.int64, device=dev)
+        kept_pos = torch.empty(nc, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = torch.empty(max(A.lib().xdrg_rpc_pending_retire_workspace_size(nc), 16), dtype=torch.uint8, device=dev)
+        launch_pending_retire(self, treply, kept, kept_pos, count, ws)
+        pos = kept_pos[self.inv]  # a survivor's new table position, by old caller position
+        alive = pos >= 0
+        rank = torch.cumsum(alive, 0) - 1
+        k = int(count.item())  # the one sync
+        # survivor c is call rank[c] of pending2; the retired ones all land on a spare slot k
+        slot = torch.empty(k + 1, dtype=torch.int64, device=dev)
+        slot.scatter_(0, torch.where(alive, rank, k), torch.arange(nc, dtype=torch.int64, device=dev))
+        old_of_new = slot[:k]
+        return PendingCalls.from_device(kept[:k], pos[old_of_new], last_xid=self.last_xid), old_of_new
+
 
 # ------------------------------------------------ the client's call stream
 @dataclass
@@ -802,3 +839,92 @@ def call_stat_message(h) -> str:
     if a in (A.RPCR_GARBAGE_RES, A.RPCR_MALFORMED, A.RPCR_NOT_REPLY):
         return "unable to unmarshal reply value sent by server"
     raise ValueError("no call stands behind this reply (ignoring reply to unknown call)")
+
+
+# -------------------------------------------------- settling a reply batch
+CALL_STAT_DTYPE = A.CALL_STAT_DTYPE
+
+
+def launch_call_stats(hdrs: torch.Tensor, reply_of: torch.Tensor, stats: torch.Tensor,
+                      unanswered: int = A.RPCS_PENDING, stream=None) -> None:
+    """xdrg_rpc_call_stats as it is: hdrs after launch_verify_results,
+    `reply_of` int64 [ncalls] in TABLE positions (launch_match_replies'),
+    stats int64 [ncalls] (xdrg_rpc_call_stat records, table order).  Kernels
+    only: capturable."""
+    A.check(A.lib().xdrg_rpc_call_stats(_ptr(hdrs), hdrs.numel() // A.RPC_HDR_BYTES, _ptr(reply_of),
+                                        reply_of.numel(), unanswered, _ptr(stats),
+                                        _stream() if stream is None else stream), "xdrg_rpc_call_stats")
+
+
+def launch_pending_retire(pending: PendingCalls, reply_of: torch.Tensor, kept: torch.Tensor,
+                          kept_pos: torch.Tensor | None, count: torch.Tensor, ws: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_pending_retire as it is: `reply_of` int64 [ncalls] in TABLE
+    positions, kept int64 [ncalls] (xdrg_rpc_call records), kept_pos int64
+    [ncalls] in TABLE positions or None, count int64 [1], ws uint8 of
+    xdrg_rpc_pending_retire_workspace_size(ncalls) bytes.  Kernels only:
+    capturable."""
+    A.check(A.lib().xdrg_rpc_pending_retire(_ptr(pending.table), pending.ncalls, _ptr(reply_of), _ptr(kept),
+                                            _ptr(kept_pos), _ptr(count), _ptr(ws), ws.numel(),
+                                            _stream() if stream is None else stream), "xdrg_rpc_pending_retire")
+
+
+def call_stats(hdrs: torch.Tensor, reply_of: torch.Tensor, pending: PendingCalls,
+               aborted: bool = False) -> torch.Tensor:
+    """The call_result the callback of asynchronous_client_base::invoke
+    receives for every pending call (rpc_call_stat(hdr), rpc_msg.cc:69-90;
+    xdrg_rpc_call_stats): an int64 device tensor [ncalls] of
+    xdrg_rpc_call_stat records (call_stats_numpy) in the caller's positions.
+    hdrs: the batch's headers after verify_results; reply_of:
+    match_replies()'s, in the caller's positions.  A call without a reply is
+    RPCS_PENDING, or with aborted=True RPCS_NETWORK_ERROR (abort_all_calls,
+    msgsock.cc:190-200)."""
+    stats = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=hdrs.device)[:pending.ncalls]
+    if pending.ncalls == 0:
+        return stats
+    treply = torch.empty_like(reply_of)
+    treply[pending.inv] = reply_of
+    launch_call_stats(hdrs, treply, stats, A.RPCS_NETWORK_ERROR if aborted else A.RPCS_PENDING)
+    return stats[pending.inv]
+
+
+def call_stats_numpy(stats: torch.Tensor) -> np.ndarray:
+    """Device xdrg_rpc_call_stat array -> numpy structured array (copies)."""
+    return stats.cpu().numpy().view(CALL_STAT_DTYPE).reshape(-1)
+
+
+def call_stat_text(type: int, stat: int = 0) -> str:
+    """rpc_call_stat::message() (rpc_msg.cc:92-112) of an xdrg_rpc_call_stat."""
+    t = int(type)
+    if t == A.RPCS_ACCEPT_STAT:
+        return rpc_errmsg_accept(stat)
+    if t == A.RPCS_AUTH_STAT:
+        return rpc_errmsg_auth(stat)
+    if t == A.RPCS_RPCVERS_MISMATCH:
+        return "server reported rpcvers field with wrong value"
+    if t == A.RPCS_GARBAGE_RES:
+        return "unable to unmarshal reply value sent by server"
+    if t == A.RPCS_NETWORK_ERROR:
+        return "network error when communicating with server"
+    if t == A.RPCS_BAD_ALLOC:
+        return "insufficient memory to unmarshal result"
+    if t == A.RPCS_PENDING:
+        raise ValueError("the call is still pending: no rpc_call_stat yet")
+    raise ValueError(f"rpc_call_stat: invalid type {t}")
+
+
+def settle(stream_bytes: torch.Tensor, offsets: torch.Tensor, pending: PendingCalls,
+           plans: dict[int, Plan | None], aborted: bool = False, stack_limit: int = A.DEFAULT_STACK_LIMIT):
+    """A reply batch settled: decode_results, then call_stats, then
+    PendingCalls.retire.  Returns (stats, results, pending2, old_of_new):
+    stats as call_stats() gives them, results decode_results' dictionary,
+    pending2 the table for the next round.  aborted=True is abort_all_calls
+    (msgsock.cc:190-200) after the batch: every call still outstanding is
+    RPCS_NETWORK_ERROR, pending2 is the empty table and old_of_new is empty;
+    the stats of answered calls are the same either way."""
+    hdrs, _, reply_of, results = decode_results(stream_bytes, offsets, pending, plans, stack_limit)
+    stats = call_stats(hdrs, reply_of, pending, aborted)
+    if aborted:
+        e = torch.empty(0, dtype=torch.int64, device=pending.device)
+        return stats, results, PendingCalls.from_device(e, e.clone(), last_xid=pending.last_xid), e.clone()
+    pending2, old_of_new = pending.retire(reply_of)
+    return stats, results, pending2, old_of_new
