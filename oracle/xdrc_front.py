@@ -507,7 +507,9 @@ class Spec:
                 order.append(d[1].id)
             elif d[0] == "program":
                 self.programs.append(d[1])
-        for name in order:
+        # structs first: a union that reaches itself through a struct's container (an arm `node *next` of a
+        # union that is a field of node) then resolves from the struct, which is declared before its fields
+        for name in sorted(order, key=lambda n: self._ast[n][0] != "struct"):
             self._resolve(name)
 
     def _resolve(self, name: str) -> XdrType:
@@ -578,6 +580,9 @@ class Spec:
         if d.type == "string":
             return String(self._val(d.bound))
         t = self._spec(d.type, d.id)
+        if isinstance(t, Struct) and not t.fields and d.qual not in ("vec", "ptr"):
+            # a struct still being defined, held by value: it may refer to itself through a container only
+            t = _Recursive(t.name)
         if d.qual == "array":
             return XArray(t, self._val(d.bound))
         if d.qual == "vec":

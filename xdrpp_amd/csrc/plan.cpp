@@ -400,6 +400,30 @@ int compile_plan(xdrg_plan &p) {
         stk.pop_back();
       }
       p.deep = frames[0] > XDRG_SUB_FRAMES;
+      // The size walk hands a long tail chain that ends its record to the
+      // chain pass (sub_kernels.h "Chains"), whose lanes size nodes at guessed
+      // addresses, each from the chain op's body to that op again.  A lane
+      // whose guess is no node reads arbitrary bytes: the walk must then meet
+      // nothing it would follow, so the op's body is the op's own region (two
+      // types that point to each other never come back to it) and holds no
+      // other element subroutine (a tree's left pointer, whose count at a wrong
+      // guess is walked element by element).  Only an op of a region that some
+      // container enters can replace a frame, and so start such a chain.
+      std::vector<uint8_t> entered(nreg, 0);
+      for (const xdrg_op &op : p.ops)
+        if (op.kind == XDRG_OP_VECTOR && (op.flags & XDRG_F_SUB)) entered[R.id[op.arg4]] = 1;
+      const uint32_t nops_all = uint32_t(p.ops.size());
+      for (uint32_t i = 0; i < nops_all; ++i) {
+        const xdrg_op &v = p.ops[i];
+        if (v.kind != XDRG_OP_VECTOR || !(v.flags & XDRG_F_SUB) || v.arg0 != 1u || !entered[R.id[i]]) continue;
+        uint32_t q = i + 1;
+        while (p.ops[q].kind == XDRG_OP_JUMP) q = p.ops[q].arg0;
+        if (p.ops[q].kind != XDRG_OP_END) continue;  // (not a tail container: never handed over)
+        const uint32_t body = R.id[v.arg4];
+        if (body != R.id[i]) p.chain_pass = false;
+        for (uint32_t j = body ? R.end[body - 1] + 1 : 0; j < R.end[body]; ++j)
+          if (j != i && p.ops[j].kind == XDRG_OP_VECTOR && (p.ops[j].flags & XDRG_F_SUB)) p.chain_pass = false;
+      }
     }
     // plans whose walks never need the deep passes (no recursive type):
     // each group of 64 records packs its decoded arrays back to back, every

@@ -137,6 +137,8 @@ struct xdrg_plan {
   bool packed = false;            // decoded element arrays packed per 64-record group (no F_SUB)
   bool deep = false;              // subroutines can nest past XDRG_SUB_FRAMES (recursive types):
                                   // the frame walks add their deep passes (sub_kernels.h)
+  bool chain_pass = true;         // deep plans: a long tail chain may go to the size walk's chain pass
+                                  // (every chain node's walk to its link meets no other container)
   uint32_t heap_factor = 0;       // decode element-area factor (xdrg_decode_heap_size)
   bool has_checks = false;
   bool has_bool = false;

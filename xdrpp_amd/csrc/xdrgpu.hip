@@ -1922,7 +1922,7 @@ int deep_setup(const xdrg_plan &p, uint64_t n, void *area, size_t area_bytes, hi
   dp.main.node_cnt = cnt + 3;
   dp.main.chain_cap = kChainCap;
   dp.main.node_cap = kNodeCap;
-  dp.main.heads = dp.main.nodes + kNodeCap;
+  dp.main.heads = p.chain_pass ? dp.main.nodes + kNodeCap : nullptr;  // (null: every lane logs its own chain)
   dp.A = sub_pass{la, cnt, lb, cnt + 1, sa, kDeepSlabA, 0};
   dp.B = sub_pass{lb, cnt + 1, nullptr, nullptr, sb, kDeepSlabB, 1};
   return XDRG_OK;
