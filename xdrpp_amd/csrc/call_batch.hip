@@ -17,36 +17,16 @@
 // kernel-argument area).
 #include <hip/hip_runtime.h>
 
-#include "plan.h"
 #include "call_batch_kernels.h"
+#include "host_common.h"
 
 namespace {
 
 using namespace xdrg;
 using namespace xdrg::dev;
-
-#define HIPCHK(x)                                                             \
-  do {                                                                        \
-    hipError_t e_ = (x);                                                      \
-    if (e_ != hipSuccess) return xdrg::record_hip_error(int(e_), #x);         \
-  } while (0)
+using namespace xdrg::host;
 
 static_assert(sizeof(xdrg_rpc_arg_src) == 64, "xdrg_rpc_arg_src is 64 bytes");
-static_assert(sizeof(cb_claim_table) < 4096 && sizeof(cb_emit_table) + 64 < 4096, "kernel arguments under 4 KiB");
-
-bool misaligned(const void *p, uintptr_t mask) { return reinterpret_cast<uintptr_t>(p) & mask; }
-
-// [a, a + an) and [b, b + bn) share a byte
-bool overlap(const void *a, uint64_t an, const void *b, uint64_t bn) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return an && bn && x < y + bn && y < x + an;
-}
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-// owner words (n), then per 256-position tile the message bytes and the winners (nb + 1 each)
-size_t cb_ws_owner(uint64_t n) { return align256(n * 8); }
-size_t cb_ws_tiles(uint64_t n) { return align256(((n + kCbThreads - 1) / kCbThreads + 1) * 8); }
-size_t cb_ws_bytes(uint64_t n) { return cb_ws_owner(n) + 2 * cb_ws_tiles(n); }
 
 }  // namespace
 
@@ -65,7 +45,7 @@ int xdrg_rpc_next_xids(const xdrg_rpc_call *d_calls, uint64_t ncalls, uint32_t l
   return XDRG_OK;
 }
 
-size_t xdrg_rpc_call_batch_workspace_size(uint64_t n) { return cb_ws_bytes(n); }
+size_t xdrg_rpc_call_batch_workspace_size(uint64_t n) { return stream_ws_bytes(n); }
 
 int xdrg_rpc_call_batch(const uint32_t *d_xids, uint64_t n, const xdrg_rpc_arg_src *srcs, uint32_t nsrcs,
                         void *d_out, uint64_t out_capacity, uint64_t *d_offsets, xdrg_rpc_call *d_sent,
@@ -73,44 +53,26 @@ int xdrg_rpc_call_batch(const uint32_t *d_xids, uint64_t n, const xdrg_rpc_arg_s
                         void *stream) {
   if (!d_offsets || !d_status || (n && !d_xids) || (nsrcs && !srcs) || nsrcs > XDRG_RPC_MAX_ARG_SRCS)
     return XDRG_EINVAL;
-  for (uint32_t k = 0; k < nsrcs; ++k) {
-    const xdrg_rpc_arg_src &S = srcs[k];
-    if (S.count_cap && !S.d_index) return XDRG_EINVAL;
-    if (!S.d_bytes && S.fixed_size) return XDRG_EINVAL;
-    if (S.d_bytes && !S.d_offsets && (!S.fixed_size || (S.fixed_size & 3u))) return XDRG_EINVAL;
-  }
+  if (!valid_srcs(srcs, nsrcs)) return XDRG_EINVAL;
   if (!d_out && out_capacity) return XDRG_EINVAL;
   if (misaligned(d_xids, 3) || misaligned(d_offsets, 7) || misaligned(d_sent, 7) || misaligned(d_counts, 7) ||
       misaligned(d_workspace, 7) || misaligned(d_out, 3))
     return XDRG_EALIGN;
-  for (uint32_t k = 0; k < nsrcs; ++k)
-    if (misaligned(srcs[k].d_bytes, 3) || misaligned(srcs[k].d_offsets, 7) || misaligned(srcs[k].d_index, 7) ||
-        misaligned(srcs[k].d_count, 7))
-      return XDRG_EALIGN;
-  if (n && (!d_workspace || workspace_bytes < cb_ws_bytes(n))) return XDRG_ESPACE;
-  const uint64_t nb = (n + kCbThreads - 1) / kCbThreads;
+  if (misaligned_srcs(srcs, nsrcs)) return XDRG_EALIGN;
+  if (n && (!d_workspace || workspace_bytes < stream_ws_bytes(n))) return XDRG_ESPACE;
+  const uint64_t nb = tiles_of(n);
   if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
 
-  cb_claim_table C = {};
+  src_claim_table C = {};
+  src_count_table N = {};
   cb_size_table Z = {};
   cb_emit_table E = {};
-  cb_count_table N = {};
-  uint64_t cblocks = 0;
-  for (uint32_t k = 0; k < nsrcs; ++k) {
-    const xdrg_rpc_arg_src &S = srcs[k];
-    const bool has = S.d_bytes != nullptr;  // a procedure without arguments: every span is [0, 0)
-    const uint64_t *offs = has ? S.d_offsets : nullptr;
-    const uint32_t fixed = has ? S.fixed_size : 0u;
-    C.e[k] = cb_claim_src{S.d_index, S.d_count, offs, S.bytes_len, S.count_cap, fixed};
-    Z.e[k] = cb_size_src{offs, fixed};
-    E.e[k] = cb_emit_src{S.d_bytes, offs, fixed, S.res, S.prog, S.vers, S.proc, 0u};
-    N.count[k] = S.d_count;
-    N.cap[k] = S.count_cap;
-    C.blk[k] = uint32_t(cblocks);
-    cblocks += (uint64_t(S.count_cap) + kCbThreads - 1) / kCbThreads;
-  }
+  const uint64_t cblocks = build_src_tables(
+      srcs, nsrcs, C, N, [&](uint32_t k, const xdrg_rpc_arg_src &S, const uint64_t *offs, uint32_t fixed) {
+        Z.e[k] = cb_size_src{offs, fixed};
+        E.e[k] = cb_emit_src{S.d_bytes, offs, fixed, S.res, S.prog, S.vers, S.proc, 0u};
+      });
   if (cblocks > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-  for (uint32_t k = nsrcs; k <= XDRG_RPC_MAX_ARG_SRCS; ++k) C.blk[k] = uint32_t(cblocks);
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto *counts = reinterpret_cast<unsigned long long *>(d_counts);
@@ -118,27 +80,28 @@ int xdrg_rpc_call_batch(const uint32_t *d_xids, uint64_t n, const xdrg_rpc_arg_s
     HIPCHK(static_cast<hipError_t>(fill32(d_offsets, 0u, 2, stream)));
     HIPCHK(static_cast<hipError_t>(fill32(&d_status->total_bytes, 0u, 2, stream)));
     if (counts) {
-      k_cb_count_entries<<<1, 64, 0, s>>>(N, nsrcs, counts);
+      k_src_count_entries<><<<1, 64, 0, s>>>(N, nsrcs, counts, counts + 1);
       HIPCHK(hipGetLastError());
     }
     return XDRG_OK;
   }
   auto *owner = static_cast<unsigned long long *>(d_workspace);
-  auto *tiles = owner + cb_ws_owner(n) / 8;
-  auto *won = tiles + cb_ws_tiles(n) / 8;
-  k_cb_fill<<<uint32_t(nb), kCbThreads, 0, s>>>(owner, n);
+  auto *tiles = owner + ws_owner(n) / 8;
+  auto *won = tiles + ws_tiles(n) / 8;
+  k_owner_fill<><<<uint32_t(nb), kTileThreads, 0, s>>>(owner, n);
   HIPCHK(hipGetLastError());
   if (cblocks) {
-    k_cb_claim<<<uint32_t(cblocks), kCbThreads, 0, s>>>(n, C, nsrcs, owner);
+    k_src_claim<<<uint32_t(cblocks), kTileThreads, 0, s>>>(n, C, nsrcs, cb_usable{}, owner);
     HIPCHK(hipGetLastError());
   }
-  k_cb_sizes<<<uint32_t(nb), kCbThreads, 0, s>>>(n, owner, Z, tiles, won);
+  k_cb_sizes<<<uint32_t(nb), kTileThreads, 0, s>>>(n, owner, Z, tiles, won);
   HIPCHK(hipGetLastError());
-  k_cb_scan<<<1, 1024, 0, s>>>(tiles, won, nb, n, N, nsrcs, d_offsets + n, d_status, counts);
+  k_tile_scan<1, 2><<<1, kScanThreads, 0, s>>>(
+      tiles, won, nb, stream_totals{N, nsrcs, n, d_offsets + n, d_status, counts, counts ? counts + 1 : nullptr});
   HIPCHK(hipGetLastError());
-  k_cb_emit<<<uint32_t(nb), kCbThreads, 0, s>>>(d_xids, n, owner, E, static_cast<uint8_t *>(d_out), out_capacity,
-                                               d_offsets, d_sent, tiles,
-                                               reinterpret_cast<unsigned long long *>(&d_status->first_error));
+  k_cb_emit<<<uint32_t(nb), kTileThreads, 0, s>>>(d_xids, n, owner, E, static_cast<uint8_t *>(d_out), out_capacity,
+                                                 d_offsets, d_sent, tiles,
+                                                 reinterpret_cast<unsigned long long *>(&d_status->first_error));
   HIPCHK(hipGetLastError());
   return XDRG_OK;
 }

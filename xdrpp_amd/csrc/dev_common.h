@@ -170,6 +170,15 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
   x = dpp_add<0x143, 0xc>(x);  // row_bcast:31 -> rows 2, 3
   return x;
 }
+// The same over 64-bit values, by __shfl_up.
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x) {
+  const uint32_t lane = __lane_id();
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t y = __shfl_up(x, o, 64);
+    if (lane >= static_cast<uint32_t>(o)) x += y;
+  }
+  return x;
+}
 
 // Packed element areas (plans with no recursive type; oracle/
 // xdr_oracle.c rec_ebytes): the wave's 64 records are one group, whose
@@ -190,11 +199,7 @@ __device__ __forceinline__ uint64_t packed_area(uint64_t E, bool bad, uint64_t a
   const uint32_t lane = __lane_id();
   const unsigned long long bm = __ballot(bad);
   if (bm & ((2ull << lane) - 1ull)) E = 0;  // a bad record at or before this one
-  uint64_t inc = E;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t x = __shfl_up(inc, o, 64);
-    if (lane >= static_cast<uint32_t>(o)) inc += x;
-  }
+  const uint64_t inc = wave_incl_scan64(E);
   const uint64_t g0 = (ebase + static_cast<uint64_t>(F) * a0 + 7u) & ~7ull;
   ecur = g0 + inc - E;
   eend = g0 + inc;

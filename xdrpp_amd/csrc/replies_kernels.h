@@ -16,18 +16,12 @@
 //   k_rpc_verify_results   the reply callback of arpc.h:59-90, one matched
 //       reply per lane, each with its call's result plan: archive(g, *res),
 //       g.done(), and GARBAGE_RES for the reply that throws (arpc.h:87-89).
-//   k_gather_res_*   one result type's bytes as an indexed stream (the
-//       tiles, scan and coalesced emit of verify_kernels.h's k_gather_*).
+//   gather_res_key   one result type's bytes as an indexed stream: the
+//       selector of verify_kernels.h's k_gather_count / k_gather_emit.
 //
 // A header is rewritten through its first 16 bytes (xid, action | err |
 // mtype, w[0], w[1]): one 16-byte load, one 16-byte store when it changes.
 #pragma once
-// verify_kernels.h defines its three gather kernels as plain (external)
-// functions, and verify.hip already holds them: this translation unit gets
-// its own copies under other names.  k_gather_scan is launched from here too.
-#define k_gather_count k_gather_count_rtu
-#define k_gather_scan k_gather_scan_rtu
-#define k_gather_emit k_gather_emit_rtu
 #include "verify_kernels.h"
 
 namespace xdrg {
@@ -183,109 +177,20 @@ __global__ __launch_bounds__(SUB ? kVerifySubThreads : kVerifyThreads) void k_rp
 }
 
 // ---------------------------------------------------------- result gather
+// The results of one type (the gather of verify_kernels.h with this
+// selector): a matched reply that is still OK, of a call with this result
+// type.
 struct gather_res_key {
   const unsigned long long *call;
   const xdrg_rpc_call *calls;
   uint64_t ncalls;
   uint32_t res;
+  __device__ __forceinline__ bool operator()(const xdrg_rpc_hdr *h, uint64_t i) const {
+    if (h->action != XDRG_RPCR_OK) return false;
+    const unsigned long long c = call[i];
+    return c < ncalls && calls[c].res == res;
+  }
 };
-
-// Selected: a matched reply that is still OK, of a call with this result
-// type, its result inside the stream.
-__device__ __forceinline__ bool gather_res_sel(const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t i, uint64_t n,
-                                               uint64_t len, const gather_res_key &K, uint64_t *src,
-                                               uint64_t *bytes) {
-  *src = 0;
-  *bytes = 0;
-  if (i >= n) return false;
-  const xdrg_rpc_hdr *h = hdrs + i;
-  if (h->action != XDRG_RPCR_OK) return false;
-  const unsigned long long c = K.call[i];
-  if (c >= K.ncalls || K.calls[c].res != K.res) return false;
-  const uint64_t a = h->body_off, b = h->end;
-  if (b < a || b > len) return false;
-  *src = a;
-  *bytes = b - a;
-  return true;
-}
-
-__global__ __launch_bounds__(kGatherThreads) void k_gather_res_count(
-    const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n, uint64_t len, gather_res_key K,
-    unsigned long long *__restrict__ tile_cnt, unsigned long long *__restrict__ tile_bytes) {
-  __shared__ unsigned long long wc[kGatherThreads / 64], wb[kGatherThreads / 64];
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kGatherThreads + threadIdx.x;
-  uint64_t src, bytes;
-  const bool sel = gather_res_sel(hdrs, i, n, len, K, &src, &bytes);
-  unsigned long long c = sel ? 1u : 0u, t = bytes;
-  for (int o = 32; o > 0; o >>= 1) {
-    c += __shfl_xor(c, o, 64);
-    t += __shfl_xor(t, o, 64);
-  }
-  if ((threadIdx.x & 63u) == 0u) { wc[threadIdx.x >> 6] = c; wb[threadIdx.x >> 6] = t; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long sc = 0, sb = 0;
-    for (uint32_t k = 0; k < kGatherThreads / 64; ++k) { sc += wc[k]; sb += wb[k]; }
-    tile_cnt[blockIdx.x] = sc;
-    tile_bytes[blockIdx.x] = sb;
-  }
-}
-
-// k_gather_emit with the result selection: index and offsets a lane per
-// header, the bytes a wave per run of 64 headers, 4 bytes a lane per step.
-__global__ __launch_bounds__(kGatherThreads) void k_gather_res_emit(
-    const uint8_t *__restrict__ xdr, uint64_t len, const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n,
-    gather_res_key K, uint8_t *__restrict__ out, uint64_t cap, uint64_t *__restrict__ offsets,
-    uint64_t *__restrict__ index, const unsigned long long *__restrict__ tile_cnt,
-    const unsigned long long *__restrict__ tile_bytes, unsigned long long *err) {
-  __shared__ unsigned long long wc[kGatherThreads / 64], wb[kGatherThreads / 64];
-  __shared__ unsigned long long s_end[kGatherThreads], s_src[kGatherThreads];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kGatherThreads + tid;
-  uint64_t src, bytes;
-  const bool sel = gather_res_sel(hdrs, i, n, len, K, &src, &bytes);
-  const uint64_t ic = wave_incl_scan64(sel ? 1u : 0u), ib = wave_incl_scan64(bytes);
-  if (lane == 63u) { wc[wid] = ic; wb[wid] = ib; }
-  __syncthreads();
-  uint64_t kbase = tile_cnt[blockIdx.x], wbase = tile_bytes[blockIdx.x];
-  for (uint32_t k = 0; k < wid; ++k) { kbase += wc[k]; wbase += wb[k]; }
-  const uint64_t at = wbase + ib - bytes;  // wbase: where the wave's stretch starts
-  bool fits = false;
-  if (sel) {
-    const uint64_t k = kbase + ic - 1u;
-    index[k] = i;
-    offsets[k] = at;
-    fits = at <= cap && bytes <= cap - at;
-    if (!fits) {  // xdr_generic_put::check (marshal.h:104-108)
-      const unsigned long long key = (static_cast<unsigned long long>(i) << 24) |
-                                     (static_cast<unsigned long long>(kOpRecordLevel) << 8) | XDRG_ERR_OVERFLOW_PUT;
-      atomicMin(err, key);
-    }
-  }
-  // the results that fit are a prefix of the wave's stretch
-  const uint64_t cb = fits ? bytes : 0u;
-  const uint64_t ie = wave_incl_scan64(cb);
-  unsigned long long *w_end = s_end + 64u * wid, *w_src = s_src + 64u * wid;
-  w_end[lane] = ie;
-  w_src[lane] = src;
-  const bool words = __ballot(fits && ((src | bytes) & 3u)) == 0ull &&
-                     !((reinterpret_cast<uintptr_t>(xdr) | (reinterpret_cast<uintptr_t>(out) + wbase)) & 3u);
-  __syncthreads();
-  const uint64_t total = w_end[63];
-  const uint32_t unit = words ? 4u : 1u;
-  for (uint64_t off = static_cast<uint64_t>(lane) * unit; off < total; off += 64u * unit) {
-    uint32_t lo = 0, hi = 63;  // the first message whose end is past `off`
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (w_end[mid] > off) hi = mid; else lo = mid + 1;
-    }
-    const uint64_t start = lo ? w_end[lo - 1] : 0u;
-    const uint8_t *s = xdr + w_src[lo] + (off - start);
-    uint8_t *d = out + wbase + off;
-    if (words) st32(d, ld32(s));
-    else *d = *s;
-  }
-}
 
 }  // namespace dev
 }  // namespace xdrg

@@ -20,7 +20,7 @@
 //       writes its 0, 24, 28 or 36-byte message at its scanned offset.
 #include <hip/hip_runtime.h>
 
-#include "plan.h"
+#include "host_common.h"
 
 namespace {
 
@@ -371,12 +371,6 @@ __global__ __launch_bounds__(256) void k_rpc_reply_emit(
 // block sums, then their exclusive scan
 size_t replies_ws_half(uint64_t n) { return (((n + 255) / 256 + 1) * 8 + 255) / 256 * 256; }
 size_t replies_ws_bytes(uint64_t n) { return 2 * replies_ws_half(n); }
-
-#define HIPCHK(x)                                                             \
-  do {                                                                        \
-    hipError_t e_ = (x);                                                      \
-    if (e_ != hipSuccess) return xdrg::record_hip_error(int(e_), #x);         \
-  } while (0)
 
 int hdr_launch(bool client, const void *d_stream, uint64_t len, const uint64_t *d_offsets,
                uint64_t n, const xdrg_rpc_proc *d_procs, uint32_t nprocs, const uint32_t *d_xids,

@@ -15,33 +15,19 @@
 // (no memset or memcpy nodes: xdrgpu.h "Graph capture") and keep no state.
 #include <hip/hip_runtime.h>
 
-#include "plan.h"
+#include "host_common.h"
 #include "settle_kernels.h"
 
 namespace {
 
 using namespace xdrg;
 using namespace xdrg::dev;
-
-#define HIPCHK(x)                                                             \
-  do {                                                                        \
-    hipError_t e_ = (x);                                                      \
-    if (e_ != hipSuccess) return xdrg::record_hip_error(int(e_), #x);         \
-  } while (0)
+using namespace xdrg::host;
 
 static_assert(sizeof(xdrg_rpc_call_stat) == 8, "xdrg_rpc_call_stat is 8 bytes");
 
-bool misaligned(const void *p, uintptr_t mask) { return reinterpret_cast<uintptr_t>(p) & mask; }
-
-// [a, a + an) and [b, b + bn) share a byte
-bool overlap(const void *a, uint64_t an, const void *b, uint64_t bn) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return an && bn && x < y + bn && y < x + an;
-}
-
-uint64_t st_tiles(uint64_t ncalls) { return (ncalls + kStThreads - 1) / kStThreads; }
 // the kept entries of every tile, one word each
-size_t st_ws_bytes(uint64_t ncalls) { return (st_tiles(ncalls) * 8 + 255) / 256 * 256; }
+size_t st_ws_bytes(uint64_t ncalls) { return align256(tiles_of(ncalls) * 8); }
 
 }  // namespace
 
@@ -53,9 +39,9 @@ int xdrg_rpc_call_stats(const xdrg_rpc_hdr *d_hdrs, uint64_t n, const uint64_t *
   if (ncalls && (!d_reply_of || !d_stats || (n && !d_hdrs))) return XDRG_EINVAL;
   if (misaligned(d_hdrs, 15) || misaligned(d_reply_of, 7) || misaligned(d_stats, 7)) return XDRG_EALIGN;
   if (ncalls == 0) return XDRG_OK;
-  const uint64_t nb = st_tiles(ncalls);
+  const uint64_t nb = tiles_of(ncalls);
   if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-  k_st_call_stats<<<uint32_t(nb), kStThreads, 0, static_cast<hipStream_t>(stream)>>>(d_hdrs, n, d_reply_of, ncalls,
+  k_st_call_stats<<<uint32_t(nb), kTileThreads, 0, static_cast<hipStream_t>(stream)>>>(d_hdrs, n, d_reply_of, ncalls,
                                                                                    unanswered, d_stats);
   HIPCHK(hipGetLastError());
   return XDRG_OK;
@@ -73,19 +59,19 @@ int xdrg_rpc_pending_retire(const xdrg_rpc_call *d_calls, uint64_t ncalls, const
       misaligned(d_count, 7) || misaligned(d_workspace, 7))
     return XDRG_EALIGN;
   if (ncalls && (!d_workspace || workspace_bytes < st_ws_bytes(ncalls))) return XDRG_ESPACE;
-  const uint64_t nb = st_tiles(ncalls);
+  const uint64_t nb = tiles_of(ncalls);
   if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto *tiles = static_cast<unsigned long long *>(d_workspace);
   if (nb) {
-    k_st_count<<<uint32_t(nb), kStThreads, 0, s>>>(d_reply_of, ncalls, tiles);
+    k_st_count<<<uint32_t(nb), kTileThreads, 0, s>>>(d_reply_of, ncalls, tiles);
     HIPCHK(hipGetLastError());
   }
-  k_st_scan<<<1, kStScanThreads, 0, s>>>(tiles, nb, d_count);  // nb == 0: the count alone
+  k_tile_scan<1, 1><<<1, kScanThreads, 0, s>>>(tiles, nullptr, nb, count_total{d_count});  // nb == 0: the count alone
   HIPCHK(hipGetLastError());
   if (nb) {
-    k_st_scatter<<<uint32_t(nb), kStThreads, 0, s>>>(d_calls, ncalls, d_reply_of, tiles, d_kept, d_kept_pos);
+    k_st_scatter<<<uint32_t(nb), kTileThreads, 0, s>>>(d_calls, ncalls, d_reply_of, tiles, d_kept, d_kept_pos);
     HIPCHK(hipGetLastError());
   }
   return XDRG_OK;

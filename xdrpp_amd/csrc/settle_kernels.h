@@ -8,11 +8,11 @@
 //
 //   k_st_call_stats  one lane per table entry: its rpc_call_stat from the
 //                    header of the message that answers it
-//   k_st_count       the kept entries (no reply) of every 256-entry tile: a
-//                    64-bit ballot per wave, summed over the tile's waves
-//   k_st_scan        exclusive scan in place of the tile counts in one
-//                    workgroup of 1024; the total to *count (also with no
-//                    tile at all: an empty table still gets its 0 from here)
+//   k_st_count       the kept entries (no reply) of every 256-entry tile
+//                    (tile_reduce)
+//   k_tile_scan<1, 1, count_total>   exclusive scan in place of the tile
+//                    counts; the total to *count (also with no tile at all:
+//                    an empty table still gets its 0 from here)
 //   k_st_scatter     one lane per entry: its rank is the kept lanes below it
 //                    in its wave's ballot, plus the waves before it in the
 //                    tile (LDS), plus the tile's base; kept entries leave as
@@ -21,34 +21,20 @@
 // No atomic anywhere: the order is the table's, and the result is a function
 // of the inputs only.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include "dev_common.h"
+#include "batch_kernels.h"
 
 namespace xdrg {
 namespace dev {
-
-constexpr uint32_t kStThreads = 256;       // entries a tile
-constexpr uint32_t kStScanThreads = 1024;  // tiles a round of the scan
-
-__device__ __forceinline__ uint64_t st_incl_scan64(uint64_t x) {
-  const uint32_t lane = __lane_id();
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o, 64);
-    if (lane >= static_cast<uint32_t>(o)) x += y;
-  }
-  return x;
-}
 
 // ------------------------------------------------------------- call stats
 // rpc_call_stat(hdr) (rpc_msg.cc:69-90) after xdrg_rpc_verify_results: every
 // action a matched reply cannot carry is GARBAGE_RES, as is a reply_of that
 // names no message of this batch (no header is read for it).
-__global__ __launch_bounds__(kStThreads) void k_st_call_stats(const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n,
+__global__ __launch_bounds__(kTileThreads) void k_st_call_stats(const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n,
                                                               const uint64_t *__restrict__ reply_of,
                                                               uint64_t ncalls, uint32_t unanswered,
                                                               xdrg_rpc_call_stat *__restrict__ stats) {
-  const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kStThreads + threadIdx.x;
+  const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   if (c >= ncalls) return;
   const uint64_t i = reply_of[c];
   xdrg_rpc_call_stat s = {XDRG_RPCS_GARBAGE_RES, 0u};
@@ -73,57 +59,23 @@ __global__ __launch_bounds__(kStThreads) void k_st_call_stats(const xdrg_rpc_hdr
 }
 
 // ---------------------------------------------------------------- retire
-__global__ __launch_bounds__(kStThreads) void k_st_count(const uint64_t *__restrict__ reply_of, uint64_t ncalls,
+__global__ __launch_bounds__(kTileThreads) void k_st_count(const uint64_t *__restrict__ reply_of, uint64_t ncalls,
                                                          unsigned long long *__restrict__ tile_kept) {
-  __shared__ uint32_t wk[kStThreads / 64];
-  const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kStThreads + threadIdx.x;
-  const bool keep = j < ncalls && reply_of[j] == XDRG_RPC_NO_CALL;
-  const unsigned long long m = __ballot(keep);
-  if ((threadIdx.x & 63u) == 0u) wk[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t s = 0;
-    for (uint32_t k = 0; k < kStThreads / 64; ++k) s += wk[k];
-    tile_kept[blockIdx.x] = s;
-  }
-}
-
-// Exclusive scan in place of the nb tile counts, kStScanThreads a round with
-// the carry of the rounds before; the total to *count.  One workgroup.
-__global__ __launch_bounds__(kStScanThreads) void k_st_scan(unsigned long long *__restrict__ tile_kept, uint64_t nb,
-                                                            uint64_t *__restrict__ count) {
-  __shared__ unsigned long long wb[kStScanThreads / 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-  unsigned long long carry = 0;
-  for (uint64_t t0 = 0; t0 < nb; t0 += kStScanThreads) {
-    const uint64_t j = t0 + tid;
-    const unsigned long long b = j < nb ? tile_kept[j] : 0ull;
-    const unsigned long long ib = st_incl_scan64(b);
-    if (lane == 63u) wb[wid] = ib;
-    __syncthreads();
-    unsigned long long bb = carry, tb = 0;
-    for (uint32_t k = 0; k < kStScanThreads / 64; ++k) {
-      if (k < wid) bb += wb[k];
-      tb += wb[k];
-    }
-    if (j < nb) tile_kept[j] = bb + ib - b;
-    carry += tb;
-    __syncthreads();  // wb reused by the next round
-  }
-  if (tid == 0) *count = carry;
+  const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
+  tile_reduce(0, j < ncalls && reply_of[j] == XDRG_RPC_NO_CALL, nullptr, tile_kept);
 }
 
 // A kept entry's rank is at most its own position (the entries before it that
 // are kept), so every store stays below ncalls; the compare keeps it there
 // even when reply_of changes between the passes.
-__global__ __launch_bounds__(kStThreads) void k_st_scatter(const xdrg_rpc_call *__restrict__ calls, uint64_t ncalls,
+__global__ __launch_bounds__(kTileThreads) void k_st_scatter(const xdrg_rpc_call *__restrict__ calls, uint64_t ncalls,
                                                            const uint64_t *__restrict__ reply_of,
                                                            const unsigned long long *__restrict__ tile_base,
                                                            xdrg_rpc_call *__restrict__ kept,
                                                            uint64_t *__restrict__ kept_pos) {
-  __shared__ uint32_t wk[kStThreads / 64];
+  __shared__ uint32_t wk[kTileThreads / 64];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-  const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kStThreads + tid;
+  const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kTileThreads + tid;
   const bool keep = j < ncalls && reply_of[j] == XDRG_RPC_NO_CALL;
   const unsigned long long m = __ballot(keep);
   if (lane == 0u) wk[wid] = __popcll(m);

@@ -14,29 +14,11 @@
 // capture") and keeps no state.
 #include <hip/hip_runtime.h>
 
-#include "plan.h"
-#include "verify_kernels.h"
-
-namespace {
+#include "verify_host.h"
 
 using namespace xdrg;
 using namespace xdrg::dev;
-
-#define HIPCHK(x)                                                             \
-  do {                                                                        \
-    hipError_t e_ = (x);                                                      \
-    if (e_ != hipSuccess) return xdrg::record_hip_error(int(e_), #x);         \
-  } while (0)
-
-// Dynamic LDS a workgroup may ask for without opting in to more.
-constexpr size_t kLdsBudget = 48u << 10;
-
-bool misaligned(const void *p, uintptr_t mask) { return reinterpret_cast<uintptr_t>(p) & mask; }
-
-// tile counts, then tile bytes (each nb + 1 u64, 256-byte aligned)
-size_t gather_ws_half(uint64_t n) { return (((n + kGatherThreads - 1) / kGatherThreads + 1) * 8 + 255) / 256 * 256; }
-
-}  // namespace
+using namespace xdrg::host;
 
 extern "C" {
 
@@ -54,23 +36,17 @@ int xdrg_verify(const xdrg_plan *plan, const void *d_xdr, uint64_t xdr_len, cons
   if (rc != XDRG_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d_bad_count) HIPCHK(static_cast<hipError_t>(fill32(d_bad_count, 0u, 2, stream)));
-  const bool sub = plan->has_sub;
-  const uint32_t nt = sub ? kVerifySubThreads : kVerifyThreads;
-  const uint64_t nb = (n + nt - 1) / nt;
-  if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
   const uint32_t nops = uint32_t(plan->ops.size());
-  const size_t frames = sub ? 4u * verify_frame_words(nt) : 0u;
-  const size_t ops_lds = size_t(nops) * sizeof(xdrg_op);
-  const bool lds_ops_fit = ops_lds + frames <= kLdsBudget;
-  const size_t lds = frames + (lds_ops_fit ? ops_lds : 0u);
+  const verify_geom g = verify_geometry(plan->has_sub, size_t(nops) * sizeof(xdrg_op), n);
+  if (g.nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
   const uint8_t *x8 = static_cast<const uint8_t *>(d_xdr);
   auto *bad = reinterpret_cast<unsigned long long *>(d_bad_count);
   const uint64_t s8 = span_stride / 8u;
-#define XDRG_VERIFY(SUB, LDSOPS)                                                                              \
-  k_verify<SUB, LDSOPS><<<uint32_t(nb), nt, lds, s>>>(x8, xdr_len, d_begin, d_end, s8, n, T->d_ops, nops,     \
-                                                      T->d_table, stack_limit, d_verdicts, bad)
-  if (sub) { if (lds_ops_fit) XDRG_VERIFY(true, true); else XDRG_VERIFY(true, false); }
-  else { if (lds_ops_fit) XDRG_VERIFY(false, true); else XDRG_VERIFY(false, false); }
+#define XDRG_VERIFY(SUB, LDSOPS)                                                                             \
+  k_verify<SUB, LDSOPS><<<uint32_t(g.nb), g.nt, g.lds, s>>>(x8, xdr_len, d_begin, d_end, s8, n, T->d_ops, nops, \
+                                                            T->d_table, stack_limit, d_verdicts, bad)
+  if (plan->has_sub) { if (g.lds_ops) XDRG_VERIFY(true, true); else XDRG_VERIFY(true, false); }
+  else { if (g.lds_ops) XDRG_VERIFY(false, true); else XDRG_VERIFY(false, false); }
 #undef XDRG_VERIFY
   HIPCHK(hipGetLastError());
   return XDRG_OK;
@@ -103,25 +79,21 @@ int xdrg_rpc_verify_args(const void *d_stream, uint64_t len, xdrg_rpc_hdr *d_hdr
     sub = sub || plans[i].plan->has_sub;
     ops_lds += plans[i].plan->ops.size() * sizeof(xdrg_op);
   }
-  const uint32_t nt = sub ? kVerifySubThreads : kVerifyThreads;
-  const uint64_t nb = (n + nt - 1) / nt;
-  if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
+  const verify_geom g = verify_geometry(sub, ops_lds, n);  // every plan's ops, staged per workgroup
+  if (g.nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint8_t *x8 = static_cast<const uint8_t *>(d_stream);
-  const size_t frames = sub ? 4u * verify_frame_words(nt) : 0u;
-  const bool lds_ops_fit = ops_lds + frames <= kLdsBudget;  // every plan's ops, staged per workgroup
-  const size_t lds = frames + (lds_ops_fit ? ops_lds : 0u);
-#define XDRG_VERIFY_ARGS(SUB, LDSOPS)                                                                        \
-  k_rpc_verify_args<SUB, LDSOPS><<<uint32_t(nb), nt, lds, s>>>(x8, len, d_hdrs, n, tab, nplans, stack_limit, \
-                                                               d_verdicts)
-  if (sub) { if (lds_ops_fit) XDRG_VERIFY_ARGS(true, true); else XDRG_VERIFY_ARGS(true, false); }
-  else { if (lds_ops_fit) XDRG_VERIFY_ARGS(false, true); else XDRG_VERIFY_ARGS(false, false); }
+#define XDRG_VERIFY_ARGS(SUB, LDSOPS)                                                                   \
+  k_rpc_verify_args<SUB, LDSOPS><<<uint32_t(g.nb), g.nt, g.lds, s>>>(x8, len, d_hdrs, n, tab, nplans, \
+                                                                     stack_limit, d_verdicts)
+  if (sub) { if (g.lds_ops) XDRG_VERIFY_ARGS(true, true); else XDRG_VERIFY_ARGS(true, false); }
+  else { if (g.lds_ops) XDRG_VERIFY_ARGS(false, true); else XDRG_VERIFY_ARGS(false, false); }
 #undef XDRG_VERIFY_ARGS
   HIPCHK(hipGetLastError());
   return XDRG_OK;
 }
 
-size_t xdrg_rpc_gather_workspace_size(uint64_t n) { return 2 * gather_ws_half(n); }
+size_t xdrg_rpc_gather_workspace_size(uint64_t n) { return gather_ws_bytes(n); }
 
 int xdrg_rpc_gather_args(const void *d_stream, uint64_t len, const xdrg_rpc_hdr *d_hdrs, uint64_t n,
                          uint32_t prog, uint32_t vers, uint32_t proc, uint8_t *d_args, uint64_t args_capacity,
@@ -133,29 +105,8 @@ int xdrg_rpc_gather_args(const void *d_stream, uint64_t len, const xdrg_rpc_hdr 
   if (misaligned(d_hdrs, 15) || misaligned(d_offsets, 7) || misaligned(d_index, 7) || misaligned(d_count, 7) ||
       misaligned(d_workspace, 7))
     return XDRG_EALIGN;
-  if (n == 0) {
-    HIPCHK(static_cast<hipError_t>(fill32(d_offsets, 0u, 2, stream)));
-    HIPCHK(static_cast<hipError_t>(fill32(d_count, 0u, 2, stream)));
-    HIPCHK(static_cast<hipError_t>(fill32(&d_status->total_bytes, 0u, 2, stream)));
-    return XDRG_OK;
-  }
-  if (!d_workspace || workspace_bytes < 2 * gather_ws_half(n)) return XDRG_ESPACE;
-  const uint64_t nb = (n + kGatherThreads - 1) / kGatherThreads;
-  if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  auto *tcnt = static_cast<unsigned long long *>(d_workspace);
-  auto *tbytes = tcnt + gather_ws_half(n) / 8;
-  const gather_key K{prog, vers, proc};
-  const uint8_t *x8 = static_cast<const uint8_t *>(d_stream);
-  k_gather_count<<<uint32_t(nb), kGatherThreads, 0, s>>>(d_hdrs, n, len, K, tcnt, tbytes);
-  HIPCHK(hipGetLastError());
-  k_gather_scan<<<1, 1024, 0, s>>>(tcnt, tbytes, nb, d_count, d_offsets, d_status);
-  HIPCHK(hipGetLastError());
-  k_gather_emit<<<uint32_t(nb), kGatherThreads, 0, s>>>(
-      x8, len, d_hdrs, n, K, d_args, args_capacity, d_offsets, d_index, tcnt, tbytes,
-      reinterpret_cast<unsigned long long *>(&d_status->first_error));
-  HIPCHK(hipGetLastError());
-  return XDRG_OK;
+  return launch_gather(gather_key{prog, vers, proc}, d_stream, len, d_hdrs, n, d_args, args_capacity, d_offsets,
+                       d_index, d_count, d_workspace, workspace_bytes, d_status, stream);
 }
 
 }  // extern "C"

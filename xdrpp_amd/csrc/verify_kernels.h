@@ -30,6 +30,7 @@
 #pragma once
 #include <type_traits>
 
+#include "batch_kernels.h"
 #include "elem_kernels.h"
 
 namespace xdrg {
@@ -350,155 +351,88 @@ __global__ __launch_bounds__(SUB ? kVerifySubThreads : kVerifyThreads) void k_rp
 }
 
 // ---------------------------------------------------- RPC argument gather
-// The calls of one procedure, in message order, as an indexed stream: per
-// 256-header tile the count of selected headers and their argument bytes
-// (k_gather_count), the exclusive scan of both (k_gather_scan, one
-// workgroup), then index, offsets and the bytes (k_gather_emit).
-constexpr uint32_t kGatherThreads = 256;
+// The headers a selector picks, in message order, as an indexed stream: per
+// 256-header tile the count of selected headers and their body bytes
+// (k_gather_count), the exclusive scan of both (k_tile_scan<2, 2,
+// gather_totals>), then index, offsets and the bytes (k_gather_emit).  SEL is
+// gather_key here, gather_res_key in replies_kernels.h.
 
+// The calls of one procedure: dispatched, with the key's numbers.
 struct gather_key {
   uint32_t prog, vers, proc;
+  __device__ __forceinline__ bool operator()(const xdrg_rpc_hdr *h, uint64_t) const {
+    return h->action == XDRG_RPC_DISPATCH && h->w[XDRG_RPC_W_PROG] == prog && h->w[XDRG_RPC_W_VERS] == vers &&
+           h->w[XDRG_RPC_W_PROC] == proc;
+  }
 };
 
-// Selected: dispatched, the key's procedure, and its arguments inside the
-// stream (a header with end < body_off or end > len is skipped: nothing of
-// it is read).  *bytes = its argument bytes.
-__device__ __forceinline__ bool gather_sel(const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t i, uint64_t n,
-                                           uint64_t len, const gather_key &K, uint64_t *src, uint64_t *bytes) {
+// Selected: a header K picks whose body lies inside the stream (a header with
+// end < body_off or end > len is skipped: nothing of it is read).  *bytes =
+// its body bytes.
+template <class SEL>
+__device__ __forceinline__ bool gather_sel(const SEL &K, const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t i,
+                                           uint64_t n, uint64_t len, uint64_t *src, uint64_t *bytes) {
   *src = 0;
   *bytes = 0;
-  if (i >= n) return false;
-  const xdrg_rpc_hdr *h = hdrs + i;
-  if (h->action != XDRG_RPC_DISPATCH || h->w[XDRG_RPC_W_PROG] != K.prog || h->w[XDRG_RPC_W_VERS] != K.vers ||
-      h->w[XDRG_RPC_W_PROC] != K.proc)
-    return false;
-  const uint64_t a = h->body_off, b = h->end;
+  if (i >= n || !K(hdrs + i, i)) return false;
+  const uint64_t a = hdrs[i].body_off, b = hdrs[i].end;
   if (b < a || b > len) return false;
   *src = a;
   *bytes = b - a;
   return true;
 }
 
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x) {
-  const uint32_t lane = __lane_id();
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o, 64);
-    if (lane >= static_cast<uint32_t>(o)) x += y;
-  }
-  return x;
-}
-
-__global__ __launch_bounds__(kGatherThreads) void k_gather_count(
-    const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n, uint64_t len, gather_key K,
-    unsigned long long *__restrict__ tile_cnt, unsigned long long *__restrict__ tile_bytes) {
-  __shared__ unsigned long long wc[kGatherThreads / 64], wb[kGatherThreads / 64];
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kGatherThreads + threadIdx.x;
+template <class SEL>
+__global__ __launch_bounds__(kTileThreads) void k_gather_count(const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n,
+                                                               uint64_t len, const SEL K,
+                                                               unsigned long long *__restrict__ tile_cnt,
+                                                               unsigned long long *__restrict__ tile_bytes) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + threadIdx.x;
   uint64_t src, bytes;
-  const bool sel = gather_sel(hdrs, i, n, len, K, &src, &bytes);
-  unsigned long long c = sel ? 1u : 0u, t = bytes;
-  for (int o = 32; o > 0; o >>= 1) {
-    c += __shfl_xor(c, o, 64);
-    t += __shfl_xor(t, o, 64);
-  }
-  if ((threadIdx.x & 63u) == 0u) { wc[threadIdx.x >> 6] = c; wb[threadIdx.x >> 6] = t; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long sc = 0, sb = 0;
-    for (uint32_t k = 0; k < kGatherThreads / 64; ++k) { sc += wc[k]; sb += wb[k]; }
-    tile_cnt[blockIdx.x] = sc;
-    tile_bytes[blockIdx.x] = sb;
-  }
-}
-
-// Exclusive scan in place of the nb tile counts and tile bytes; the totals to
-// *count, offsets[count] and status->total_bytes.  One workgroup of 1024.
-__global__ __launch_bounds__(1024) void k_gather_scan(unsigned long long *__restrict__ tile_cnt,
-                                                      unsigned long long *__restrict__ tile_bytes, uint64_t nb,
-                                                      uint64_t *__restrict__ count, uint64_t *__restrict__ offsets,
-                                                      xdrg_status *status) {
-  __shared__ unsigned long long wc[16], wb[16];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-  unsigned long long carry_c = 0, carry_b = 0;
-  for (uint64_t t0 = 0; t0 < nb; t0 += 1024u) {
-    const uint64_t j = t0 + tid;
-    const unsigned long long c = j < nb ? tile_cnt[j] : 0ull, b = j < nb ? tile_bytes[j] : 0ull;
-    const unsigned long long ic = wave_incl_scan64(c), ib = wave_incl_scan64(b);
-    if (lane == 63u) { wc[wid] = ic; wb[wid] = ib; }
-    __syncthreads();
-    unsigned long long bc = carry_c, bb = carry_b, tc = 0, tb = 0;
-    for (uint32_t k = 0; k < 16; ++k) {
-      if (k < wid) { bc += wc[k]; bb += wb[k]; }
-      tc += wc[k];
-      tb += wb[k];
-    }
-    if (j < nb) { tile_cnt[j] = bc + ic - c; tile_bytes[j] = bb + ib - b; }
-    carry_c += tc;
-    carry_b += tb;
-    __syncthreads();  // wc / wb reused by the next tile
-  }
-  if (tid == 0) {
-    *count = carry_c;
-    offsets[carry_c] = carry_b;
-    status->total_bytes = carry_b;
-  }
+  const bool sel = gather_sel(K, hdrs, i, n, len, &src, &bytes);
+  tile_reduce(bytes, sel, tile_bytes, tile_cnt);
 }
 
 // Index and offsets a lane per header; the bytes a wave per run of 64
-// headers: its selected arguments are one contiguous stretch of the output,
+// headers: its selected bodies are one contiguous stretch of the output,
 // written 4 bytes a lane per step (coalesced), each word's message found by
-// a binary search of the wave's 64 byte ends in LDS.  Arguments that are not
-// whole aligned words (forged headers) go byte by byte the same way.  An
-// argument that does not fit the capacity is XDRG_ERR_OVERFLOW_PUT at its
-// message (nothing of it is written, nor of the ones after it).
-__global__ __launch_bounds__(kGatherThreads) void k_gather_emit(
-    const uint8_t *__restrict__ xdr, uint64_t len, const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n,
-    gather_key K, uint8_t *__restrict__ args, uint64_t cap, uint64_t *__restrict__ offsets,
-    uint64_t *__restrict__ index, const unsigned long long *__restrict__ tile_cnt,
-    const unsigned long long *__restrict__ tile_bytes, unsigned long long *err) {
-  __shared__ unsigned long long wc[kGatherThreads / 64], wb[kGatherThreads / 64];
-  __shared__ unsigned long long s_end[kGatherThreads], s_src[kGatherThreads];
+// stretch_find.  Bodies that are not whole aligned words (forged headers) go
+// byte by byte the same way.  A body that does not fit the capacity is
+// XDRG_ERR_OVERFLOW_PUT at its message (stretch_place).
+template <class SEL>
+__global__ __launch_bounds__(kTileThreads) void k_gather_emit(
+    const uint8_t *__restrict__ xdr, uint64_t len, const xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n, const SEL K,
+    uint8_t *__restrict__ out, uint64_t cap, uint64_t *__restrict__ offsets, uint64_t *__restrict__ index,
+    const unsigned long long *__restrict__ tile_cnt, const unsigned long long *__restrict__ tile_bytes,
+    unsigned long long *err) {
+  __shared__ unsigned long long wc[kTileThreads / 64];
+  __shared__ unsigned long long s_end[kTileThreads], s_src[kTileThreads];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kGatherThreads + tid;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTileThreads + tid;
   uint64_t src, bytes;
-  const bool sel = gather_sel(hdrs, i, n, len, K, &src, &bytes);
-  const uint64_t ic = wave_incl_scan64(sel ? 1u : 0u), ib = wave_incl_scan64(bytes);
-  if (lane == 63u) { wc[wid] = ic; wb[wid] = ib; }
-  __syncthreads();
-  uint64_t kbase = tile_cnt[blockIdx.x], wbase = tile_bytes[blockIdx.x];
-  for (uint32_t k = 0; k < wid; ++k) { kbase += wc[k]; wbase += wb[k]; }
-  const uint64_t at = wbase + ib - bytes;  // wbase: where the wave's stretch starts
-  bool fits = false;
-  if (sel) {
-    const uint64_t k = kbase + ic - 1u;
-    index[k] = i;
-    offsets[k] = at;
-    fits = at <= cap && bytes <= cap - at;
-    if (!fits) {  // xdr_generic_put::check (marshal.h:104-108)
-      const unsigned long long key = (static_cast<unsigned long long>(i) << 24) |
-                                     (static_cast<unsigned long long>(kOpRecordLevel) << 8) | XDRG_ERR_OVERFLOW_PUT;
-      atomicMin(err, key);
-    }
-  }
-  // the arguments that fit are a prefix of the wave's stretch
-  const uint64_t cb = fits ? bytes : 0u;
-  const uint64_t ie = wave_incl_scan64(cb);
+  const bool sel = gather_sel(K, hdrs, i, n, len, &src, &bytes);
+  const uint64_t ic = wave_incl_scan64(sel ? 1u : 0u);
+  if (lane == 63u) wc[wid] = ic;  // read in put(), after stretch_place's barrier
   unsigned long long *w_end = s_end + 64u * wid, *w_src = s_src + 64u * wid;
-  w_end[lane] = ie;
+  const stretch_at p = stretch_place(bytes, sel, i, tile_bytes, cap, err, w_end, [&](uint64_t at) {
+    uint64_t k = tile_cnt[blockIdx.x] + ic - 1u;
+    for (uint32_t w = 0; w < wid; ++w) k += wc[w];
+    if (sel) {
+      index[k] = i;
+      offsets[k] = at;
+    }
+  });
   w_src[lane] = src;
-  const bool words = __ballot(fits && ((src | bytes) & 3u)) == 0ull &&
-                     !((reinterpret_cast<uintptr_t>(xdr) | (reinterpret_cast<uintptr_t>(args) + wbase)) & 3u);
+  const bool words = __ballot(p.fits && ((src | bytes) & 3u)) == 0ull &&
+                     !((reinterpret_cast<uintptr_t>(xdr) | (reinterpret_cast<uintptr_t>(out) + p.wbase)) & 3u);
   __syncthreads();
   const uint64_t total = w_end[63];
   const uint32_t unit = words ? 4u : 1u;
   for (uint64_t off = static_cast<uint64_t>(lane) * unit; off < total; off += 64u * unit) {
-    uint32_t lo = 0, hi = 63;  // the first message whose end is past `off`
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (w_end[mid] > off) hi = mid; else lo = mid + 1;
-    }
-    const uint64_t start = lo ? w_end[lo - 1] : 0u;
-    const uint8_t *s = xdr + w_src[lo] + (off - start);
-    uint8_t *d = args + wbase + off;
+    const uint32_t m = stretch_find(w_end, off);
+    const uint64_t start = m ? w_end[m - 1] : 0u;
+    const uint8_t *s = xdr + w_src[m] + (off - start);
+    uint8_t *d = out + p.wbase + off;
     if (words) st32(d, ld32(s));
     else *d = *s;
   }

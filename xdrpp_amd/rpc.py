@@ -311,8 +311,56 @@ def decode_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tupl
 
 
 # ------------------------------------------------------ the reply stream
+class _Source:
+    """What ResultSource and ArgSource share: the output of one
+    Marshaler.encode (xdr, with offsets or fixed_size) and the message of each
+    of its entries (index, count, count_cap).  _what: the call and the noun of
+    the error messages."""
+    _what = ("", "")
+
+    @property
+    def cap(self) -> int:
+        return self.index.numel() if self.count_cap is None else self.count_cap
+
+    @classmethod
+    def _encoded(cls, index: torch.Tensor, xdr, offsets_or_fixed_size) -> tuple:
+        """(xdr, offsets, fixed_size) from result_source()'s and arg_source()'s
+        last two arguments."""
+        if isinstance(xdr, EncodeResult):
+            if offsets_or_fixed_size is None:
+                offsets_or_fixed_size = xdr.offsets
+            xdr = xdr.xdr
+        if xdr is None:
+            return None, None, 0
+        if isinstance(offsets_or_fixed_size, torch.Tensor):
+            return xdr, offsets_or_fixed_size, 0
+        if offsets_or_fixed_size is None:
+            if index.numel() == 0 or xdr.numel() % index.numel():
+                raise ValueError("%s: fixed-size %s need their wire size" % cls._what)
+            offsets_or_fixed_size = xdr.numel() // index.numel()
+        return xdr, None, int(offsets_or_fixed_size)
+
+    def _fields(self) -> tuple:
+        """The fields xdrg_rpc_result_src and xdrg_rpc_arg_src start with."""
+        if self.xdr is None or self.xdr.numel() == 0:  # no bytes: void results, a procedure without arguments
+            if self.cap and self.fixed_size:
+                raise ValueError("%s: fixed-size %s without bytes" % self._what)
+            return None, None, _ptr(self.index), _ptr(self.count), 0, self.cap, 0
+        return (_ptr(self.xdr), _ptr(self.offsets), _ptr(self.index), _ptr(self.count), self.xdr.numel(), self.cap,
+                self.fixed_size)
+
+
+def _src_array(sources, ctype, limit: int, noun: str, extra) -> "C.Array":
+    if len(sources) > limit:
+        raise ValueError(f"at most {limit} {noun} sources per call")
+    arr = (ctype * max(len(sources), 1))()
+    for k, r in enumerate(sources):
+        arr[k] = ctype(*r._fields(), *extra(r))
+    return arr
+
+
 @dataclass
-class ResultSource:
+class ResultSource(_Source):
     """One xdrg_rpc_result_src: the results of one Marshaler.encode and the
     message each of them answers.  index: int64 [count] message numbers
     (gather_args' index).  xdr: the encoded results, None for void results.
@@ -325,25 +373,11 @@ class ResultSource:
     fixed_size: int = 0
     count: torch.Tensor | None = None
     count_cap: int | None = None
-
-    @property
-    def cap(self) -> int:
-        return self.index.numel() if self.count_cap is None else self.count_cap
+    _what = ("reply_batch", "results")
 
 
 def _result_srcs(sources) -> "C.Array":
-    if len(sources) > A.RPC_MAX_RESULT_SRCS:
-        raise ValueError(f"at most {A.RPC_MAX_RESULT_SRCS} result sources per call")
-    arr = (A.XdrgRpcResultSrc * max(len(sources), 1))()
-    for k, r in enumerate(sources):
-        if r.xdr is None or r.xdr.numel() == 0:  # no bytes: void results
-            if r.cap and r.fixed_size:
-                raise ValueError("reply_batch: fixed-size results without bytes")
-            arr[k] = A.XdrgRpcResultSrc(None, None, _ptr(r.index), _ptr(r.count), 0, r.cap, 0)
-            continue
-        arr[k] = A.XdrgRpcResultSrc(_ptr(r.xdr), _ptr(r.offsets), _ptr(r.index), _ptr(r.count),
-                                    r.xdr.numel(), r.cap, r.fixed_size)
-    return arr
+    return _src_array(sources, A.XdrgRpcResultSrc, A.RPC_MAX_RESULT_SRCS, "result", lambda r: ())
 
 
 def launch_reply_batch(hdrs: torch.Tensor, sources: list[ResultSource], out: torch.Tensor, offsets: torch.Tensor,
@@ -362,19 +396,7 @@ def result_source(index: torch.Tensor, xdr=None, offsets_or_fixed_size=None) -> 
     void results, a uint8 tensor, or what Marshaler.encode returned; the last
     an int64 offsets tensor, the wire size of a fixed plan, or None (taken
     from the EncodeResult; a fixed plan's size is then bytes / count)."""
-    if isinstance(xdr, EncodeResult):
-        if offsets_or_fixed_size is None:
-            offsets_or_fixed_size = xdr.offsets
-        xdr = xdr.xdr
-    if xdr is None:
-        return ResultSource(index)
-    if isinstance(offsets_or_fixed_size, torch.Tensor):
-        return ResultSource(index, xdr, offsets_or_fixed_size)
-    if offsets_or_fixed_size is None:
-        if index.numel() == 0 or xdr.numel() % index.numel():
-            raise ValueError("reply_batch: fixed-size results need their wire size")
-        offsets_or_fixed_size = xdr.numel() // index.numel()
-    return ResultSource(index, xdr, None, int(offsets_or_fixed_size))
+    return ResultSource(index, *ResultSource._encoded(index, xdr, offsets_or_fixed_size))
 
 
 def reply_batch(hdrs: torch.Tensor, results: list, capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
@@ -533,7 +555,7 @@ class PendingCalls:
 
 # ------------------------------------------------ the client's call stream
 @dataclass
-class ArgSource:
+class ArgSource(_Source):
     """One xdrg_rpc_arg_src: the arguments of one procedure's calls, as one
     Marshaler.encode wrote them, and the call position of each.  key: (prog,
     vers, proc).  res: the number of the procedure's result type (what
@@ -550,10 +572,7 @@ class ArgSource:
     fixed_size: int = 0
     count: torch.Tensor | None = None
     count_cap: int | None = None
-
-    @property
-    def cap(self) -> int:
-        return self.index.numel() if self.count_cap is None else self.count_cap
+    _what = ("call_batch", "arguments")
 
 
 def arg_source(key, res: int, index: torch.Tensor, xdr=None, offsets_or_fixed_size=None) -> ArgSource:
@@ -562,36 +581,12 @@ def arg_source(key, res: int, index: torch.Tensor, xdr=None, offsets_or_fixed_si
     Marshaler.encode returned; the last an int64 offsets tensor, the wire size
     of a fixed plan, or None (taken from the EncodeResult; a fixed plan's size
     is then bytes / count)."""
-    key = tuple(int(v) for v in key)
-    if isinstance(xdr, EncodeResult):
-        if offsets_or_fixed_size is None:
-            offsets_or_fixed_size = xdr.offsets
-        xdr = xdr.xdr
-    if xdr is None:
-        return ArgSource(key, int(res), index)
-    if isinstance(offsets_or_fixed_size, torch.Tensor):
-        return ArgSource(key, int(res), index, xdr, offsets_or_fixed_size)
-    if offsets_or_fixed_size is None:
-        if index.numel() == 0 or xdr.numel() % index.numel():
-            raise ValueError("call_batch: fixed-size arguments need their wire size")
-        offsets_or_fixed_size = xdr.numel() // index.numel()
-    return ArgSource(key, int(res), index, xdr, None, int(offsets_or_fixed_size))
+    return ArgSource(tuple(int(v) for v in key), int(res), index,
+                     *ArgSource._encoded(index, xdr, offsets_or_fixed_size))
 
 
 def _arg_srcs(sources) -> "C.Array":
-    if len(sources) > A.RPC_MAX_ARG_SRCS:
-        raise ValueError(f"at most {A.RPC_MAX_ARG_SRCS} argument sources per call")
-    arr = (A.XdrgRpcArgSrc * max(len(sources), 1))()
-    for k, r in enumerate(sources):
-        prog, vers, proc = r.key
-        if r.xdr is None or r.xdr.numel() == 0:  # no bytes: a procedure without arguments
-            if r.cap and r.fixed_size:
-                raise ValueError("call_batch: fixed-size arguments without bytes")
-            arr[k] = A.XdrgRpcArgSrc(None, None, _ptr(r.index), _ptr(r.count), 0, r.cap, 0, prog, vers, proc, r.res)
-            continue
-        arr[k] = A.XdrgRpcArgSrc(_ptr(r.xdr), _ptr(r.offsets), _ptr(r.index), _ptr(r.count), r.xdr.numel(), r.cap,
-                                 r.fixed_size, prog, vers, proc, r.res)
-    return arr
+    return _src_array(sources, A.XdrgRpcArgSrc, A.RPC_MAX_ARG_SRCS, "argument", lambda r: (*r.key, r.res))
 
 
 def launch_next_xids(pending: PendingCalls, xids: torch.Tensor, stream=None) -> None:
