@@ -1321,6 +1321,100 @@ int xdrg_rpc_pending_retire(const xdrg_rpc_call *d_calls, uint64_t ncalls,
                             uint64_t *d_count /* device u64 */,
                             void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------- */
+/* The receive side                                                        */
+/* ---------------------------------------------------------------------- */
+/*
+ * Every stage above starts from one device buffer of whole record-marked
+ * messages.  A server or an asynchronous client has many sockets instead, each
+ * of which has handed over some number of bytes that usually ends inside a
+ * mark or inside a body.  xdrg_rpc_recv_batch is msg_sock::input
+ * (xdrpp/msgsock.cc:38-119) for all of them in one call: a partial read is
+ * kept for the next one (rdpos_, rdmsg_), every whole message is delivered
+ * (rcb_), a clear fragment bit is ECONNRESET (:86-91), a size above maxmsglen_
+ * is E2BIG as soon as the mark is read (:99-117), and what was delivered
+ * before a failure stays delivered.  With XDRG_RECV_RPC_SOCK it also applies
+ * rpc_sock::recv_msg's test (:202-225), which closes the connection at the
+ * first message shorter than 8 bytes or whose word 1 is neither CALL nor REPLY
+ * (rpc_tcp_listener_common::receive_cb, xdrpp/server.cc:152-158, deletes the
+ * socket).  One bad connection does not hide the others.
+ *
+ * Input.  Connection c's bytes are d_buf[begin, begin + len); begin is a
+ * multiple of 4, the segments are ascending and disjoint (begin[c] + len[c] <=
+ * begin[c + 1] <= buf_len), len is arbitrary (0, 1..3, not a multiple of 4:
+ * TCP delivers any count).  The table lives on the device: the kernels clamp
+ * every segment into [0, buf_len) (begin rounded down to a multiple of 4) and
+ * never read outside d_buf nor write outside the outputs, whatever it holds.
+ *
+ * Framing.  Each connection is framed on its own by the rules xdrg_index_msgs
+ * follows (read_message's order of checks, xdrpp/srpc.cc:29-55, with
+ * msg_sock's length rule), except that a cut tail is no error: the connection
+ * stays XDRG_CONN_OPEN, consumed stops at the last whole message and need
+ * says how long the tail must become.  An empty message (size 0) is
+ * delivered; its entry in the stream is its 4-byte mark.  XDRG_CONN_BAD_SIZE
+ * (the pre-swap size test of srpc.cc:38-39, or a size that is not a multiple
+ * of 4 once the body is there) has no counterpart in msg_sock itself: the
+ * next mark would not be word aligned, and every consumer's xdr_get throws
+ * xdr_bad_message_size (xdrpp/marshal.h:152-162).
+ *
+ * Output.  The delivered messages form one contiguous stream in d_out,
+ * connections in table order and each connection's messages in wire order:
+ * d_offsets[k] is message k's mark, d_offsets[n], d_status->total_bytes and
+ * *d_count carry the totals, d_conn_of[k] is message k's connection and, with
+ * XDRG_RECV_RPC_SOCK, d_kind[k] is 0 for CALL and 1 for REPLY (d_kind may be
+ * NULL without the flag).  d_out and d_offsets are what xdrg_rpc_dispatch,
+ * xdrg_rpc_check_replies, xdrg_rpc_match_replies and xdrg_decode_msgs take.
+ *
+ * Call-level errors, through d_status; neither can occur with out_capacity >=
+ * the sum of len and max_msgs >= that sum / 4.  More than max_msgs messages:
+ * XDRG_ERR_MSG_COUNT at record max_msgs; *d_count = max_msgs, the first
+ * max_msgs entries and d_offsets[max_msgs] are written.  A message that does
+ * not fit out_capacity: XDRG_ERR_OVERFLOW_PUT at that message; nothing of it
+ * nor of the ones after it is copied.  d_conns is complete in either case (it
+ * depends on the walk only), and total_bytes is what the stream needs.
+ *
+ * XDRG_EINVAL: unknown flags; NULL d_offsets, d_count or d_status; NULL d_segs
+ * or d_conns with nconns > 0, d_buf with buf_len > 0, d_out with out_capacity
+ * > 0, d_conn_of (with the flag: d_kind) with max_msgs > 0; d_out overlapping
+ * d_buf.  XDRG_EALIGN: d_buf, d_out or d_conn_of not 4-aligned, any other
+ * array not 8-aligned.  XDRG_EUNSUPPORTED: nconns > 0x7fffffff or max_msgs >=
+ * 2^40.  XDRG_ESPACE: workspace below
+ * xdrg_rpc_recv_batch_workspace_size(nconns, buf_len), which need not be
+ * initialised.  Nothing is allocated, no lock is held; kernels only.
+ */
+typedef struct xdrg_rpc_conn_in { uint64_t begin; uint64_t len; } xdrg_rpc_conn_in; /* 16 bytes */
+
+enum xdrg_conn_state {
+  XDRG_CONN_OPEN = 0,     /* nothing wrong; the tail (if any) waits for more bytes  */
+  XDRG_CONN_FRAGMENT = 1, /* fragment bit clear: ECONNRESET      msgsock.cc:86-91   */
+  XDRG_CONN_TOO_LONG = 2, /* size > max_msg_len: E2BIG           msgsock.cc:99-117  */
+  XDRG_CONN_BAD_SIZE = 3, /* a size no consumer can take (see above)                */
+  XDRG_CONN_BAD_RPC = 4   /* XDRG_RECV_RPC_SOCK only: recv_msg's test, msgsock.cc:205-224 */
+};
+
+typedef struct xdrg_rpc_conn { /* 32 bytes, one per connection, written for every connection */
+  uint64_t first;    /* index of its first message in the batch (exclusive scan of msgs) */
+  uint64_t consumed; /* bytes of its segment taken by the delivered messages; on a failure:
+                        the failing mark's offset in the segment */
+  uint64_t msgs;     /* whole messages delivered */
+  uint32_t need;     /* OPEN: 0 if the segment ends at a mark boundary, 4 if it ends inside a
+                        mark, 4 + size if it ends inside that message's body; else 0 */
+  uint32_t state;    /* enum xdrg_conn_state */
+} xdrg_rpc_conn;
+
+#define XDRG_RECV_RPC_SOCK 1u /* flags: apply rpc_sock::recv_msg's test, write d_kind */
+
+size_t xdrg_rpc_recv_batch_workspace_size(uint64_t nconns, uint64_t buf_len);
+int xdrg_rpc_recv_batch(const void *d_buf, uint64_t buf_len,
+                        const xdrg_rpc_conn_in *d_segs, uint64_t nconns,
+                        uint32_t max_msg_len, uint32_t flags,
+                        void *d_out, uint64_t out_capacity,
+                        uint64_t *d_offsets /* max_msgs + 1 */, uint64_t max_msgs, uint64_t *d_count,
+                        uint32_t *d_conn_of /* max_msgs */, uint8_t *d_kind /* max_msgs, or NULL */,
+                        xdrg_rpc_conn *d_conns /* nconns */,
+                        void *d_workspace, size_t workspace_bytes,
+                        xdrg_status *d_status, void *stream);
+
 /* Recursion depth per record: d_depths[i] = the deepest class/container
  * level record i's walk enters (the record itself is level 1), so
  * xdr::check_xdr_depth(r_i, limit) (xdrpp/depth_checker.h:72-79) is

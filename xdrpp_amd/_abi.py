@@ -146,6 +146,7 @@ EXPORTED = (
     "xdrg_rpc_reply_batch", "xdrg_rpc_reply_batch_workspace_size",
     "xdrg_rpc_next_xids", "xdrg_rpc_call_batch", "xdrg_rpc_call_batch_workspace_size", "xdrg_rpc_pending_add",
     "xdrg_rpc_call_stats", "xdrg_rpc_pending_retire", "xdrg_rpc_pending_retire_workspace_size",
+    "xdrg_rpc_recv_batch", "xdrg_rpc_recv_batch_workspace_size",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -210,6 +211,24 @@ RPCS_PENDING = 0xFFFFFFFF    # XDRG_RPCS_PENDING
 RPC_CALL_STAT_BYTES = 8      # sizeof(xdrg_rpc_call_stat)
 CALL_STAT_DTYPE = np.dtype([("type", "<u4"), ("stat", "<u4")])
 assert CALL_STAT_DTYPE.itemsize == RPC_CALL_STAT_BYTES
+
+# the receive batch (include/xdrgpu.h "The receive side")
+CONN_OPEN, CONN_FRAGMENT, CONN_TOO_LONG, CONN_BAD_SIZE, CONN_BAD_RPC = range(5)  # enum xdrg_conn_state
+RECV_RPC_SOCK = 1  # XDRG_RECV_RPC_SOCK
+
+
+class XdrgRpcConnIn(C.Structure):
+    _fields_ = [("begin", C.c_uint64), ("len", C.c_uint64)]
+
+
+class XdrgRpcConn(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("consumed", C.c_uint64), ("msgs", C.c_uint64), ("need", C.c_uint32),
+                ("state", C.c_uint32)]
+
+
+CONN_IN_DTYPE = np.dtype([("begin", "<u8"), ("len", "<u8")])
+CONN_DTYPE = np.dtype([("first", "<u8"), ("consumed", "<u8"), ("msgs", "<u8"), ("need", "<u4"), ("state", "<u4")])
+assert C.sizeof(XdrgRpcConnIn) == CONN_IN_DTYPE.itemsize == 16 and C.sizeof(XdrgRpcConn) == CONN_DTYPE.itemsize == 32
 
 
 _lib = None
@@ -315,6 +334,10 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_pending_retire_workspace_size.restype = sz
     L.xdrg_rpc_pending_retire.argtypes = [vp, u64, vp, vp, vp, vp, vp, sz, vp]
     L.xdrg_rpc_pending_retire.restype = C.c_int
+    L.xdrg_rpc_recv_batch_workspace_size.argtypes = [u64, u64]
+    L.xdrg_rpc_recv_batch_workspace_size.restype = sz
+    L.xdrg_rpc_recv_batch.argtypes = [vp, u64, vp, u64, u32, u32, vp, u64, vp, u64, vp, vp, vp, vp, vp, sz, vp, vp]
+    L.xdrg_rpc_recv_batch.restype = C.c_int
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

@@ -34,13 +34,18 @@ Host-side mirror of the reference's RPC message handling, batched:
       first reply (msgsock.cc:217-219) and abort_all_calls
       (msgsock.cc:190-200, arpc.h:60-61)                    -> call_stats(), PendingCalls.retire(),
                                                                settle()
+    msg_sock::input for many sockets at once (msgsock.cc:
+      38-119): whole messages delivered, partial tails kept,
+      a framing error closing its own connection only; and
+      rpc_sock::recv_msg's test (msgsock.cc:202-225)        -> Receiver, recv_batch(),
+                                                               Received.reply_ranges()
 
 Each header decodes to one 64-byte xdrg_rpc_hdr (HDR_DTYPE below).  The
 exceptions a client raises for a reply (xdr_call_error with the
 rpc_call_stat message, exception.h:25-57, rpc_msg.cc:8-109) come from
 raise_for_reply().  Every byte is produced by the HIP kernels of
 libxdrgpu.so (xdrpp_amd/csrc/rpc.hip, verify.hip, replies.hip,
-reply_batch.hip, call_batch.hip, settle.hip).
+reply_batch.hip, call_batch.hip, settle.hip, recv_batch.hip).
 """
 from __future__ import annotations
 
@@ -923,3 +928,175 @@ def settle(stream_bytes: torch.Tensor, offsets: torch.Tensor, pending: PendingCa
         return stats, results, PendingCalls.from_device(e, e.clone(), last_xid=pending.last_xid), e.clone()
     pending2, old_of_new = pending.retire(reply_of)
     return stats, results, pending2, old_of_new
+
+
+# ------------------------------------------------------- the receive side
+CONN_IN_DTYPE, CONN_DTYPE = A.CONN_IN_DTYPE, A.CONN_DTYPE
+CONN_STATE_NAMES = ("OPEN", "FRAGMENT", "TOO_LONG", "BAD_SIZE", "BAD_RPC")
+
+
+def check_segs(segs: np.ndarray, buf_len: int) -> np.ndarray:
+    """A host table of (begin, len) rows as xdrg_rpc_recv_batch wants it:
+    begins multiples of 4, segments ascending, disjoint and inside the buffer.
+    Raises AbiError (EINVAL) where the host can see a violation; the kernels
+    clamp whatever a device table holds."""
+    t = np.ascontiguousarray(segs).view(CONN_IN_DTYPE).reshape(-1) if np.asarray(segs).dtype == CONN_IN_DTYPE \
+        else np.array([tuple(int(v) for v in r) for r in np.asarray(segs, dtype=np.uint64).reshape(-1, 2)],
+                      dtype=CONN_IN_DTYPE)
+    b, n = t["begin"].astype(object), t["len"].astype(object)
+    ends = b + n
+    if (t["begin"] & 3).any() or any(e > buf_len for e in ends) or any(ends[i] > b[i + 1] for i in range(len(t) - 1)):
+        raise A.AbiError("xdrg_rpc_recv_batch failed: EINVAL (segments: begin a multiple of 4, ascending, "
+                         "disjoint, inside the buffer)")
+    return t
+
+
+def launch_recv_batch(buf: torch.Tensor, segs: torch.Tensor, max_msg_len: int, flags: int, out: torch.Tensor,
+                      offsets: torch.Tensor, count: torch.Tensor, conn_of: torch.Tensor, kind: torch.Tensor | None,
+                      conns: torch.Tensor, status: Status, ws: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_recv_batch as it is: buf and out uint8, segs int64 [2 nconns]
+    (xdrg_rpc_conn_in records), offsets int64 [max_msgs + 1], count int64 [1],
+    conn_of int32 [max_msgs], kind uint8 [max_msgs] or None, conns int64
+    [4 nconns] (xdrg_rpc_conn records), ws uint8 of
+    xdrg_rpc_recv_batch_workspace_size(nconns, buf.numel()) bytes.  `status`
+    is not initialised here.  Kernels only: capturable."""
+    A.check(A.lib().xdrg_rpc_recv_batch(_ptr(buf), buf.numel(), _ptr(segs), segs.numel() // 2, max_msg_len, flags,
+                                        _ptr(out), out.numel(), offsets.data_ptr(), offsets.numel() - 1,
+                                        count.data_ptr(), _ptr(conn_of), _ptr(kind), _ptr(conns), _ptr(ws),
+                                        ws.numel(), status.ptr, _stream() if stream is None else stream),
+            "xdrg_rpc_recv_batch")
+
+
+def conns_numpy(conns: torch.Tensor) -> np.ndarray:
+    """Device xdrg_rpc_conn array -> numpy structured array (copies)."""
+    return conns.cpu().numpy().view(CONN_DTYPE).reshape(-1)
+
+
+@dataclass
+class Received:
+    """What recv_batch() delivers: `stream` uint8, the whole messages of every
+    connection, connections in table order and each connection's messages in
+    wire order; `offsets` int64 [count + 1], message k's mark and then the
+    end (what dispatch, check_replies, match_replies and Marshaler.decode_msgs
+    take); `count`; `conn_of` int32 [count]; `kind` uint8 [count] (0 CALL, 1
+    REPLY) or None without rpc_sock; `conns` int64 [4 nconns], the 32-byte
+    xdrg_rpc_conn records (conns_numpy())."""
+    stream: torch.Tensor
+    offsets: torch.Tensor
+    count: int
+    conn_of: torch.Tensor
+    kind: torch.Tensor | None
+    conns: torch.Tensor
+
+    def conns_numpy(self) -> np.ndarray:
+        return conns_numpy(self.conns)
+
+    def reply_ranges(self, reply_offsets: torch.Tensor) -> np.ndarray:
+        """The byte range of a reply stream that belongs to each connection:
+        int64 [nconns, 2], row c = (reply_offsets[first[c]], reply_offsets[
+        first[c] + msgs[c]]).  reply_batch writes replies in call order and
+        the messages here are in connection order, so a connection's replies
+        are ONE contiguous range of the reply stream, ready for one writev,
+        and the ranges of consecutive connections tile the stream."""
+        c = self.conns_numpy()
+        ro = reply_offsets.cpu().numpy()
+        first = c["first"].astype(np.int64)
+        return np.stack([ro[first], ro[first + c["msgs"].astype(np.int64)]], axis=1).astype(np.int64)
+
+
+def recv_batch(buf: torch.Tensor, segs, max_msg_len: int = A.MSG_SOCK_MAXMSGLEN, rpc_sock: bool = True) -> Received:
+    """msg_sock::input for many connections at once (xdrg_rpc_recv_batch;
+    msgsock.cc:38-119, with rpc_sock=True also recv_msg's test, :202-225).
+    buf: uint8 device tensor holding every connection's received bytes; segs:
+    the (begin, len) table, a numpy array (checked on the host: AbiError for a
+    misaligned begin or segments that overlap or leave the buffer) or an int64
+    device tensor [2 nconns] (clamped by the kernels).  One sync, for the
+    totals.  Raises nothing for a connection's framing error: that closes the
+    connection (conns_numpy()["state"]) and no other."""
+    dev = buf.device
+    if not torch.is_tensor(segs):
+        t = check_segs(segs, buf.numel())
+        segs = torch.from_numpy(t.view(np.int64).copy()).to(dev)
+    nconns = segs.numel() // 2
+    total = buf.numel()
+    max_msgs = total // 4
+    L = A.lib()
+    out = torch.empty(max(total, 4), dtype=torch.uint8, device=dev)[:total]
+    offs = torch.empty(max_msgs + 1, dtype=torch.int64, device=dev)
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)
+    conn_of = torch.empty(max(max_msgs, 1), dtype=torch.int32, device=dev)[:max_msgs]
+    kind = torch.empty(max(max_msgs, 1), dtype=torch.uint8, device=dev)[:max_msgs] if rpc_sock else None
+    conns = torch.empty(max(4 * nconns, 4), dtype=torch.int64, device=dev)[:4 * nconns]
+    ws = torch.empty(max(L.xdrg_rpc_recv_batch_workspace_size(nconns, total), 16), dtype=torch.uint8, device=dev)
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    launch_recv_batch(buf, segs, max_msg_len, A.RECV_RPC_SOCK if rpc_sock else 0, out, offs, cnt, conn_of, kind,
+                      conns, st, ws, s)
+    e = st.read(s)
+    if e.code:  # cannot happen with these capacities
+        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    n = int(cnt.item())
+    return Received(out[:int(e.total_bytes)], offs[:n + 1], n, conn_of[:n], None if kind is None else kind[:n], conns)
+
+
+class Receiver:
+    """The host's rdpos_ / rdmsg_ (msgsock.h) for many connections: the bytes
+    each has received and not yet had framed.  Host code only; the framing is
+    recv_batch's.
+
+        rx.feed(conn, data)         # after each readv
+        buf, segs = rx.batch()      # pinned uint8 tensor and (begin, len) table; rx.ids[i] = the connection of row i
+        got = recv_batch(buf.to("cuda", non_blocking=True), segs)
+        rx.advance(got.conns_numpy())
+    """
+
+    def __init__(self):
+        self._tail: dict = {}    # connection -> bytearray not yet consumed
+        self._need: dict = {}    # connection -> bytes its tail must reach before it is sent again
+        self.closed: dict = {}   # connection -> xdrg_conn_state it failed with
+        self.ids: list = []      # the connection of each row of the last batch()
+
+    def feed(self, conn, data) -> None:
+        if conn in self.closed:
+            raise ValueError(f"connection {conn!r} is closed ({CONN_STATE_NAMES[self.closed[conn]]})")
+        self._tail.setdefault(conn, bytearray()).extend(bytes(data))
+
+    def pending(self, conn) -> int:
+        return len(self._tail.get(conn, b""))
+
+    def batch(self, pin: bool | None = None):
+        """Every open connection whose tail has at least `need` bytes (and any
+        at all), packed at 16-byte-aligned begins in feed order of first
+        appearance.  Returns (buf uint8 tensor, pinned where CUDA is there;
+        segs numpy CONN_IN_DTYPE); self.ids holds the connection of each row."""
+        ids = [c for c, t in self._tail.items() if len(t) and len(t) >= self._need.get(c, 0)]
+        segs = np.zeros(len(ids), dtype=CONN_IN_DTYPE)
+        at = 0
+        for i, c in enumerate(ids):
+            segs[i] = (at, len(self._tail[c]))
+            at = (at + len(self._tail[c]) + 15) & ~15
+        buf = torch.zeros(at, dtype=torch.uint8)
+        if torch.cuda.is_available() if pin is None else pin:
+            buf = buf.pin_memory()
+        view = buf.numpy()
+        for i, c in enumerate(ids):
+            b = int(segs["begin"][i])
+            view[b:b + len(self._tail[c])] = np.frombuffer(self._tail[c], dtype=np.uint8)
+        self.ids = ids
+        return buf, segs
+
+    def advance(self, conns: np.ndarray) -> None:
+        """Take the xdrg_rpc_conn records of the last batch() (row i =
+        connection self.ids[i]): drop the consumed bytes, remember need, close
+        what failed."""
+        if len(conns) != len(self.ids):
+            raise ValueError("advance() takes the records of the last batch()")
+        for c, r in zip(self.ids, conns):
+            if int(r["state"]) != A.CONN_OPEN:
+                self.closed[c] = int(r["state"])
+                self._tail.pop(c, None)
+                self._need.pop(c, None)
+                continue
+            del self._tail[c][:int(r["consumed"])]
+            self._need[c] = int(r["need"])
