@@ -1415,6 +1415,134 @@ int xdrg_rpc_recv_batch(const void *d_buf, uint64_t buf_len,
                         void *d_workspace, size_t workspace_bytes,
                         xdrg_status *d_status, void *stream);
 
+/* ---------------------------------------------------------------------- */
+/* The asynchronous client over many connections                           */
+/* ---------------------------------------------------------------------- */
+/*
+ * In the reference every connection is its own rpc_sock: its own xid_
+ * (xdrpp/msgsock.h:118-122; two fresh connections both hand out xid 1), its
+ * own calls_ (xdrpp/msgsock.cc:202-232; a reply is looked up in the calls_ of
+ * the socket it arrived on, anything else is "ignoring reply to unknown
+ * call") and its own abort_all_calls (msgsock.cc:190-200; the calls of the
+ * one socket that failed receive NETWORK_ERROR, arpc.h:60-61).  The calls
+ * below are xdrg_rpc_next_xids, xdrg_rpc_pending_add, xdrg_rpc_match_replies,
+ * xdrg_rpc_call_stats and xdrg_rpc_pending_retire for many rpc_socks at once.
+ *
+ * The table is two parallel device arrays of ncalls entries: d_calls
+ * (xdrg_rpc_call, as above) and d_sock (uint32_t, the entry's socket number),
+ * sorted ascending by (sock, xid as unsigned) with no duplicate pair -- the
+ * concatenation, in socket order, of the tables the single-socket calls take.
+ * Socket numbers are the caller's, 0..nsocks-1, stable across rounds (the rows
+ * of xdrg_rpc_recv_batch are per round).  d_call and d_reply_of name positions
+ * in this table, and xdrg_rpc_verify_results and xdrg_rpc_gather_results,
+ * which read d_calls[c].res only, take it as it is.
+ *
+ * Every call equals its single-socket sibling applied to each socket's run
+ * of the arrays on its own.  All validate on the host before any HIP call
+ * (XDRG_EINVAL: NULL required pointers; XDRG_EALIGN: u64 and call arrays not
+ * 8-aligned, u32 arrays not 4-aligned; XDRG_ESPACE: a small workspace),
+ * launch kernels only (no memset or memcpy node, no wait, no state; capturable
+ * on one stream) and neither read nor write outside the given arrays,
+ * whatever these hold: a socket number at or past nsocks indexes nothing.
+ */
+
+/*
+ * get_xid() followed by send_call (msgsock.h:118-122) for a batch of n calls
+ * grouped by socket: d_call_sock[k] is call k's socket, non-decreasing.  With
+ * [a, b) the run of socket g in d_call_sock and [lo, hi) its run in d_sock,
+ * d_xids[k] for a <= k < b is what xdrg_rpc_next_xids(d_calls + lo, hi - lo,
+ * d_last[g], b - a, ...) writes at k - a, the skip of a pending 0 included.
+ * d_last holds every rpc_sock's xid_.  d_last_out (may be NULL; must not
+ * alias d_last) receives xid_ after the batch for EVERY g < nsocks, written by
+ * lanes of the call: the last xid of g's run, or d_last[g] when it has none.
+ * A call whose socket is >= nsocks counts from 0 over that socket's run of
+ * the table.  The call stream itself is xdrg_rpc_call_batch over d_xids,
+ * unchanged: with the positions in socket order, socket g's bytes are
+ * [d_offsets[a], d_offsets[b]), one writev per connection.
+ * XDRG_EINVAL also: ncalls + n > 0xffffffff, nsocks > 0xffffffff, d_last_out
+ * equal to or overlapping d_last.  An unsorted d_call_sock gives unspecified
+ * xids, in bounds.  n == 0: d_last_out is still written.
+ */
+int xdrg_rpc_socks_next_xids(const xdrg_rpc_call *d_calls, const uint32_t *d_sock, uint64_t ncalls,
+                             const uint32_t *d_last /* nsocks */, uint64_t nsocks,
+                             const uint32_t *d_call_sock /* n */, uint64_t n,
+                             uint32_t *d_xids /* n */, uint32_t *d_last_out /* nsocks, may be NULL */,
+                             void *stream);
+
+/*
+ * send_call's emplace (msgsock.cc:227-232) for every socket.  d_new is
+ * xdrg_rpc_call_batch's d_sent, d_new_sock the batch's d_call_sock
+ * (non-decreasing); within a socket's run the xids ascend with at most one
+ * descent (the wrap) and are disjoint from that socket's entries.  Socket g's
+ * part of the result is d_merged[lo + a, hi + b): it equals
+ * xdrg_rpc_pending_add on that socket's parts, d_merged_sock is g there, and
+ * d_old_pos / d_new_pos (may be NULL) are that call's positions plus lo + a.
+ * EVERY entry of d_new is merged, XDRG_RPC_RES_UNSENT ones included.  Arrays
+ * that break the precondition give an unspecified table inside d_merged and
+ * d_merged_sock; a position that would leave them is not written and reads
+ * XDRG_RPC_NO_CALL in d_old_pos / d_new_pos.
+ * XDRG_EINVAL also: d_merged equal to or overlapping d_calls or d_new,
+ * d_merged_sock equal to or overlapping d_sock or d_new_sock.
+ * XDRG_EUNSUPPORTED: more than 0x7fffffff workgroups.
+ */
+int xdrg_rpc_socks_pending_add(const xdrg_rpc_call *d_calls, const uint32_t *d_sock, uint64_t ncalls,
+                               const xdrg_rpc_call *d_new /* n */, const uint32_t *d_new_sock /* n */, uint64_t n,
+                               xdrg_rpc_call *d_merged /* ncalls + n */, uint32_t *d_merged_sock /* ncalls + n */,
+                               uint64_t *d_old_pos /* ncalls, may be NULL */,
+                               uint64_t *d_new_pos /* n, may be NULL */, void *stream);
+
+/*
+ * rpc_sock::recv_msg (msgsock.cc:202-232) on the socket each message arrived
+ * on.  Every rule of xdrg_rpc_match_replies holds (size < 8, CALL, any other
+ * word 1, the first reply wins by a 64-bit atomicMin, later replies are
+ * XDRG_RPCR_UNKNOWN_XID); the one difference is the lookup key, (sock, word
+ * 0), with sock = d_row_sock ? d_row_sock[d_msg_row[i]] : d_msg_row[i].
+ * d_msg_row is xdrg_rpc_recv_batch's d_conn_of; d_row_sock (may be NULL) maps
+ * the round's rows to socket numbers.  A REPLY whose row is >= nrows, or whose
+ * pair is not in the table -- an xid that is pending on another socket
+ * included -- is XDRG_RPCR_UNKNOWN_XID with XDRG_RPC_NO_CALL
+ * (msgsock.cc:212-216).
+ */
+int xdrg_rpc_socks_match_replies(const void *d_stream, uint64_t len, const uint64_t *d_offsets, uint64_t n,
+                                 const uint32_t *d_msg_row /* n */,
+                                 const uint32_t *d_row_sock /* nrows, may be NULL */, uint64_t nrows,
+                                 const xdrg_rpc_call *d_calls, const uint32_t *d_sock, uint64_t ncalls,
+                                 xdrg_rpc_hdr *d_hdrs, uint64_t *d_call /* n */,
+                                 uint64_t *d_reply_of /* ncalls */, void *stream);
+
+/*
+ * xdrg_rpc_call_stats with `unanswered` chosen per entry: d_closed[g] nonzero
+ * says abort_all_calls (msgsock.cc:190-200) ran on socket g, and a call of g
+ * without a reply is {XDRG_RPCS_NETWORK_ERROR, 0} (arpc.h:60-61); on an open
+ * socket it is {XDRG_RPCS_PENDING, 0}.  An entry whose socket is >= nsocks
+ * counts as open.  A call answered before its socket failed keeps the stat of
+ * its reply: recv_msg had erased it (msgsock.cc:217-219) before the failure.
+ */
+int xdrg_rpc_socks_call_stats(const xdrg_rpc_hdr *d_hdrs, uint64_t n,
+                              const uint64_t *d_reply_of /* ncalls */, const uint32_t *d_sock, uint64_t ncalls,
+                              const uint32_t *d_closed /* nsocks */, uint64_t nsocks,
+                              xdrg_rpc_call_stat *d_stats /* ncalls */, void *stream);
+
+/*
+ * Every calls_ after a reply batch: entry j is kept iff d_reply_of[j] ==
+ * XDRG_RPC_NO_CALL and its socket is open (d_closed as above).  d_kept and
+ * d_kept_sock receive the kept entries in table order, *d_count their number,
+ * d_kept_pos[j] (may be NULL) the new position of entry j or
+ * XDRG_RPC_NO_CALL.  The three passes of xdrg_rpc_pending_retire (tile
+ * counts, one-workgroup scan that writes *d_count, ballot ranks), no atomic,
+ * and the same workspace formula.  XDRG_EINVAL also: d_kept equal to or
+ * overlapping d_calls, d_kept_sock equal to or overlapping d_sock.
+ * XDRG_EUNSUPPORTED: more than 0x7fffffff workgroups.  ncalls == 0: *d_count
+ * = 0 is still written, by a kernel.
+ */
+size_t xdrg_rpc_socks_pending_retire_workspace_size(uint64_t ncalls);
+int xdrg_rpc_socks_pending_retire(const xdrg_rpc_call *d_calls, const uint32_t *d_sock, uint64_t ncalls,
+                                  const uint64_t *d_reply_of /* ncalls */,
+                                  const uint32_t *d_closed /* nsocks */, uint64_t nsocks,
+                                  xdrg_rpc_call *d_kept /* ncalls */, uint32_t *d_kept_sock /* ncalls */,
+                                  uint64_t *d_kept_pos /* ncalls, may be NULL */, uint64_t *d_count,
+                                  void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Recursion depth per record: d_depths[i] = the deepest class/container
  * level record i's walk enters (the record itself is level 1), so
  * xdr::check_xdr_depth(r_i, limit) (xdrpp/depth_checker.h:72-79) is

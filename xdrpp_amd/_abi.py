@@ -147,6 +147,8 @@ EXPORTED = (
     "xdrg_rpc_next_xids", "xdrg_rpc_call_batch", "xdrg_rpc_call_batch_workspace_size", "xdrg_rpc_pending_add",
     "xdrg_rpc_call_stats", "xdrg_rpc_pending_retire", "xdrg_rpc_pending_retire_workspace_size",
     "xdrg_rpc_recv_batch", "xdrg_rpc_recv_batch_workspace_size",
+    "xdrg_rpc_socks_next_xids", "xdrg_rpc_socks_pending_add", "xdrg_rpc_socks_match_replies",
+    "xdrg_rpc_socks_call_stats", "xdrg_rpc_socks_pending_retire", "xdrg_rpc_socks_pending_retire_workspace_size",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -338,6 +340,18 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_recv_batch_workspace_size.restype = sz
     L.xdrg_rpc_recv_batch.argtypes = [vp, u64, vp, u64, u32, u32, vp, u64, vp, u64, vp, vp, vp, vp, vp, sz, vp, vp]
     L.xdrg_rpc_recv_batch.restype = C.c_int
+    L.xdrg_rpc_socks_next_xids.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, vp, vp]
+    L.xdrg_rpc_socks_next_xids.restype = C.c_int
+    L.xdrg_rpc_socks_pending_add.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp]
+    L.xdrg_rpc_socks_pending_add.restype = C.c_int
+    L.xdrg_rpc_socks_match_replies.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+    L.xdrg_rpc_socks_match_replies.restype = C.c_int
+    L.xdrg_rpc_socks_call_stats.argtypes = [vp, u64, vp, vp, u64, vp, u64, vp, vp]
+    L.xdrg_rpc_socks_call_stats.restype = C.c_int
+    L.xdrg_rpc_socks_pending_retire_workspace_size.argtypes = [u64]
+    L.xdrg_rpc_socks_pending_retire_workspace_size.restype = sz
+    L.xdrg_rpc_socks_pending_retire.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]
+    L.xdrg_rpc_socks_pending_retire.restype = C.c_int
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

@@ -1100,3 +1100,322 @@ class Receiver:
                 continue
             del self._tail[c][:int(r["consumed"])]
             self._need[c] = int(r["need"])
+
+
+# --------------------------------- the asynchronous client, many connections
+class SockCalls:
+    """The calls_ of many rpc_socks in one table (include/xdrgpu.h "The
+    asynchronous client over many connections"): every outstanding call is
+    keyed by (sock, xid), `table` (xdrg_rpc_call records) and `sock` (int32
+    socket numbers) are sorted by that pair, and `last` (int32 [nsocks], on
+    the device) holds every socket's xid_ (0 in a fresh rpc_sock).  Two sockets
+    may both have xid 1 pending; a duplicate (sock, xid) raises ValueError.  As
+    PendingCalls does, it keeps the permutation, so that everything the
+    functions below take and return names a call by its position in `xids`;
+    verify_results and gather_results take it as they take a PendingCalls."""
+
+    def __init__(self, socks, xids, res, nsocks: int | None = None, device="cuda", *, last=None):
+        as_np = lambda v: v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        x = (as_np(xids).astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32)
+        g = np.broadcast_to(as_np(socks).astype(np.int64), x.shape).astype(np.int64)
+        r = np.broadcast_to(as_np(res).astype(np.int64) & 0xFFFFFFFF, x.shape).astype(np.uint32)
+        if nsocks is None:
+            nsocks = int(g.max()) + 1 if g.size else (0 if last is None else len(as_np(last).reshape(-1)))
+        if g.size and (g.min() < 0 or g.max() >= nsocks):
+            raise ValueError("SockCalls: a socket number outside 0..nsocks-1")
+        order = np.lexsort((x, g))  # stable; by sock, then by xid as unsigned
+        gs, xs = g[order], x[order]
+        if np.any((gs[1:] == gs[:-1]) & (xs[1:] == xs[:-1])):
+            raise ValueError("SockCalls: duplicate (sock, xid)")
+        t = np.empty(x.size, dtype=CALL_DTYPE)
+        t["xid"], t["res"] = xs, r[order]
+        inv = np.empty(x.size, dtype=np.int64)
+        inv[order] = np.arange(x.size, dtype=np.int64)
+        lv = np.zeros(nsocks, dtype=np.int64) if last is None else \
+            np.broadcast_to(as_np(last).astype(np.int64) & 0xFFFFFFFF, (nsocks,))
+        self.device = torch.device(device)
+        self.ncalls, self.nsocks = int(x.size), int(nsocks)
+        self.table = torch.from_numpy(t.view(np.int64).copy()).to(self.device)
+        self.sock = torch.from_numpy(gs.astype(np.int32)).to(self.device)
+        self.last = torch.from_numpy(lv.astype(np.uint32).view(np.int32).copy()).to(self.device)
+        self.perm = torch.from_numpy(order.astype(np.int64)).to(self.device)
+        self.inv = torch.from_numpy(inv).to(self.device)
+
+    @classmethod
+    def from_device(cls, table: torch.Tensor, sock: torch.Tensor, inv: torch.Tensor,
+                    last: torch.Tensor) -> "SockCalls":
+        """A table that is on the device already (xdrg_rpc_socks_pending_add's
+        d_merged and d_merged_sock, xdrg_rpc_socks_pending_retire's d_kept and
+        d_kept_sock; not checked), `inv` int64 [ncalls] the table position of
+        the caller's call c, `last` int32 [nsocks]."""
+        self = cls.__new__(cls)
+        self.device = table.device
+        self.ncalls, self.nsocks = int(table.numel()), int(last.numel())
+        self.table, self.sock, self.inv, self.last = table, sock, inv, last
+        self.perm = torch.empty_like(inv)
+        self.perm[inv] = torch.arange(self.ncalls, dtype=torch.int64, device=self.device)
+        return self
+
+    to_caller = PendingCalls.to_caller
+    to_table = PendingCalls.to_table
+
+    @property
+    def calls(self) -> np.ndarray:
+        """The sorted table on the host (copies)."""
+        return self.table.cpu().numpy().view(CALL_DTYPE).reshape(-1).copy()
+
+    def socks_numpy(self) -> np.ndarray:
+        """The socket of every table entry, on the host (copies)."""
+        return self.sock.cpu().numpy().astype(np.int64)
+
+    def last_numpy(self) -> np.ndarray:
+        return self.last.cpu().numpy().view(np.uint32).copy()
+
+    def for_sock(self, g: int, device=None) -> PendingCalls:
+        """Socket g's rpc_sock as a PendingCalls: its calls in ascending
+        caller position, its xid_ as last_xid.  Copies to the host."""
+        sk, perm, c = self.socks_numpy(), self.perm.cpu().numpy(), self.calls
+        mine = np.nonzero(sk == g)[0]
+        by_caller = mine[np.argsort(perm[mine], kind="stable")]
+        lx = int(self.last_numpy()[g]) if 0 <= g < self.nsocks else 0
+        return PendingCalls(c["xid"][by_caller], c["res"][by_caller], self.device if device is None else device,
+                            last_xid=lx)
+
+    def callers_of(self, g: int) -> np.ndarray:
+        """The caller positions of socket g's calls, ascending: call p of
+        for_sock(g) is call callers_of(g)[p] here."""
+        sk, perm = self.socks_numpy(), self.perm.cpu().numpy()
+        return np.sort(perm[sk == g])
+
+
+def launch_socks_next_xids(pending: SockCalls, call_sock: torch.Tensor, xids: torch.Tensor,
+                           last_out: torch.Tensor | None, stream=None) -> None:
+    """xdrg_rpc_socks_next_xids as it is: call_sock int32 [n] non-decreasing,
+    xids int32 [n], last_out int32 [nsocks] (not pending.last) or None.
+    Kernels only: capturable."""
+    A.check(A.lib().xdrg_rpc_socks_next_xids(_ptr(pending.table), _ptr(pending.sock), pending.ncalls,
+                                             _ptr(pending.last), pending.nsocks, _ptr(call_sock), xids.numel(),
+                                             _ptr(xids), _ptr(last_out), _stream() if stream is None else stream),
+            "xdrg_rpc_socks_next_xids")
+
+
+def launch_socks_pending_add(pending: SockCalls, new: torch.Tensor, new_sock: torch.Tensor, merged: torch.Tensor,
+                             merged_sock: torch.Tensor, old_pos: torch.Tensor | None, new_pos: torch.Tensor | None,
+                             stream=None) -> None:
+    """xdrg_rpc_socks_pending_add as it is: new int64 [n] (launch_call_batch's
+    sent), new_sock int32 [n], merged int64 and merged_sock int32 [ncalls +
+    n], old_pos int64 [ncalls] and new_pos int64 [n] in TABLE positions, or
+    None.  Kernels only: capturable."""
+    A.check(A.lib().xdrg_rpc_socks_pending_add(_ptr(pending.table), _ptr(pending.sock), pending.ncalls, _ptr(new),
+                                               _ptr(new_sock), new.numel(), _ptr(merged), _ptr(merged_sock),
+                                               _ptr(old_pos), _ptr(new_pos),
+                                               _stream() if stream is None else stream),
+            "xdrg_rpc_socks_pending_add")
+
+
+def launch_socks_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, msg_row: torch.Tensor,
+                               row_sock: torch.Tensor | None, nrows: int, pending: SockCalls, hdrs: torch.Tensor,
+                               call: torch.Tensor, reply_of: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_socks_match_replies as it is: msg_row int32 [n] (recv_batch's
+    conn_of), row_sock int32 [nrows] or None (a row is its socket), `call`
+    int64 [n] and `reply_of` int64 [ncalls] in TABLE positions.  Kernels only:
+    capturable."""
+    n = offsets.numel() - 1
+    A.check(A.lib().xdrg_rpc_socks_match_replies(_ptr(stream_bytes), stream_bytes.numel(), _ptr(offsets), n,
+                                                 _ptr(msg_row), _ptr(row_sock), nrows, _ptr(pending.table),
+                                                 _ptr(pending.sock), pending.ncalls, _ptr(hdrs), _ptr(call),
+                                                 _ptr(reply_of), _stream() if stream is None else stream),
+            "xdrg_rpc_socks_match_replies")
+
+
+def launch_socks_call_stats(hdrs: torch.Tensor, reply_of: torch.Tensor, pending: SockCalls, closed: torch.Tensor,
+                            stats: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_socks_call_stats as it is: `reply_of` int64 [ncalls] in TABLE
+    positions, closed int32 [nsocks], stats int64 [ncalls] (table order).
+    Kernels only: capturable."""
+    A.check(A.lib().xdrg_rpc_socks_call_stats(_ptr(hdrs), hdrs.numel() // A.RPC_HDR_BYTES, _ptr(reply_of),
+                                              _ptr(pending.sock), pending.ncalls, _ptr(closed), closed.numel(),
+                                              _ptr(stats), _stream() if stream is None else stream),
+            "xdrg_rpc_socks_call_stats")
+
+
+def launch_socks_pending_retire(pending: SockCalls, reply_of: torch.Tensor, closed: torch.Tensor,
+                                kept: torch.Tensor, kept_sock: torch.Tensor, kept_pos: torch.Tensor | None,
+                                count: torch.Tensor, ws: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_socks_pending_retire as it is: `reply_of` int64 [ncalls] in
+    TABLE positions, closed int32 [nsocks], kept int64 and kept_sock int32
+    [ncalls], kept_pos int64 [ncalls] or None, count int64 [1], ws uint8 of
+    xdrg_rpc_socks_pending_retire_workspace_size(ncalls) bytes.  Kernels only:
+    capturable."""
+    A.check(A.lib().xdrg_rpc_socks_pending_retire(_ptr(pending.table), _ptr(pending.sock), pending.ncalls,
+                                                  _ptr(reply_of), _ptr(closed), closed.numel(), _ptr(kept),
+                                                  _ptr(kept_sock), _ptr(kept_pos), _ptr(count), _ptr(ws), ws.numel(),
+                                                  _stream() if stream is None else stream),
+            "xdrg_rpc_socks_pending_retire")
+
+
+def _sock_tensor(socks, n: int, dev) -> torch.Tensor:
+    t = socks if isinstance(socks, torch.Tensor) else torch.from_numpy(np.asarray(socks).astype(np.int64))
+    t = t.reshape(-1).to(device=dev, dtype=torch.int32)
+    if t.numel() != n:
+        raise ValueError(f"one socket number per call: {t.numel()} for {n} calls")
+    return t.contiguous()
+
+
+def socks_call_batch(pending: SockCalls, socks, sources: list, capacity: int | None = None):
+    """call_batch() for a batch whose calls go to many connections: socks[i] is
+    call position i's socket, non-decreasing (a batch not in socket order
+    raises ValueError).  Every socket counts on from its own xid_ over its own
+    calls_ (xdrg_rpc_socks_next_xids), the stream is xdrg_rpc_call_batch's, and
+    every calls_ takes its sends (xdrg_rpc_socks_pending_add).  Returns
+    (stream, offsets int64 [n + 1], xids int32 [n], pending2, ranges): ranges
+    int64 numpy [nsocks, 2], socket g's bytes of the stream (one writev per
+    connection; the ranges tile the stream).  In pending2 the old calls keep
+    their caller positions and call i is ncalls + i.  Errors as call_batch."""
+    srcs = [r if isinstance(r, ArgSource) else arg_source(*r) for r in sources]
+    if len(srcs) > A.RPC_MAX_ARG_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_ARG_SRCS} argument sources per call")
+    dev = pending.device
+    n = len(socks) if not isinstance(socks, torch.Tensor) else socks.numel()
+    call_sock = _sock_tensor(socks, n, dev)
+    L = A.lib()
+    nc = pending.ncalls
+    cap = capacity
+    if cap is None:
+        cap = 44 * n + sum(0 if r.xdr is None else r.xdr.numel() for r in srcs)
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    xids = torch.empty(n, dtype=torch.int32, device=dev)
+    sent = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    merged = torch.empty(nc + n, dtype=torch.int64, device=dev)
+    merged_sock = torch.empty(nc + n, dtype=torch.int32, device=dev)
+    pos = torch.empty(nc + n, dtype=torch.int64, device=dev)  # old_pos, then new_pos
+    last2 = torch.empty_like(pending.last)
+    ws = torch.empty(max(L.xdrg_rpc_call_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
+    # run ends of every socket in the batch, for the ranges (and the order check)
+    ends = torch.searchsorted(call_sock.to(torch.int64),
+                              torch.arange(pending.nsocks, dtype=torch.int64, device=dev), right=True)
+    ordered = bool((call_sock[1:] >= call_sock[:-1]).all().item()) if n > 1 else True
+    if not ordered or (n and (int(call_sock[0].item()) < 0 or int(call_sock[-1].item()) >= pending.nsocks)):
+        raise ValueError("socks_call_batch: the calls must be in socket order, sockets 0..nsocks-1")
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    launch_socks_next_xids(pending, call_sock, xids, last2, s)
+    launch_call_batch(xids, srcs, out, offs, sent, counts, st, ws, s)
+    launch_socks_pending_add(pending, sent, call_sock, merged, merged_sock, pos[:nc], pos[nc:], s)
+    e = st.read(s)
+    unsent, unused = counts.tolist()
+    if unsent or unused:
+        raise ValueError(f"call_batch: {unsent} call positions without a usable entry, {unused} entries unused")
+    if e.code:
+        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    old_pos, new_pos = pos[:nc], pos[nc:]
+    inv = torch.cat([old_pos[pending.inv], new_pos])
+    pending2 = SockCalls.from_device(merged, merged_sock, inv, last2)
+    eb = offs[ends].cpu().numpy().astype(np.int64)
+    ranges = np.stack([np.concatenate([[0], eb[:-1]]) if eb.size else eb, eb], axis=1).astype(np.int64)
+    return out[:int(e.total_bytes)], offs, xids, pending2, ranges
+
+
+def _row_sock(ids, dev) -> torch.Tensor | None:
+    if ids is None:
+        return None
+    t = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.asarray(list(ids)).astype(np.int64))
+    return t.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _socks_match_t(stream_bytes, offsets, rows, pending, ids):
+    dev = stream_bytes.device
+    n = offsets.numel() - 1
+    hdrs = check_replies(stream_bytes, offsets)
+    tcall = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    reply_of = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=dev)
+    row_sock = _row_sock(ids, dev)
+    nrows = pending.nsocks if row_sock is None else row_sock.numel()
+    rows = rows.to(torch.int32).contiguous()
+    launch_socks_match_replies(stream_bytes, offsets, rows, row_sock, nrows, pending, hdrs, tcall, reply_of)
+    return hdrs, tcall[:n], reply_of[:pending.ncalls]
+
+
+def socks_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, rows: torch.Tensor, pending: SockCalls,
+                        ids=None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """match_replies() with every reply looked up in the calls_ of the socket
+    it arrived on (xdrg_rpc_socks_match_replies).  rows: int32 [n], the row of
+    every message (recv_batch's conn_of); ids: the socket number of every row
+    (Receiver.ids when the connections are named by their socket numbers), or
+    None when a row is its socket.  A reply whose xid is pending on another
+    socket only is RPCR_UNKNOWN_XID.  Returns (hdrs, call, reply_of) in the
+    caller's positions."""
+    hdrs, tcall, reply_of = _socks_match_t(stream_bytes, offsets, rows, pending, ids)
+    return hdrs, pending.to_caller(tcall), reply_of[pending.inv] if pending.ncalls else reply_of
+
+
+def closed_socks(received: Received, ids, nsocks: int, also: torch.Tensor | None = None) -> torch.Tensor:
+    """The `closed` tensor (int32 [nsocks], on the device) after a recv_batch:
+    socket ids[row] is closed when its row's state is not CONN_OPEN, i.e.
+    msg_sock::input or rpc_sock::recv_msg would have closed the connection and
+    abort_all_calls run.  also: an earlier closed tensor, kept.  Torch ops
+    only, no sync."""
+    dev = received.conns.device
+    state = received.conns.view(-1, 4)[:, 3] >> 32  # xdrg_rpc_conn.state: the high half of the last word
+    closed = torch.zeros(nsocks, dtype=torch.int32, device=dev)
+    row_sock = _row_sock(ids, dev)
+    if row_sock is not None and row_sock.numel():
+        ok = (row_sock >= 0) & (row_sock < nsocks)
+        closed.scatter_reduce_(0, row_sock.clamp(0, max(nsocks - 1, 0)).to(torch.int64),
+                               ((state != A.CONN_OPEN) & ok).to(torch.int32), reduce="amax")
+    if also is not None:
+        closed = torch.maximum(closed, (also.to(dev) != 0).to(torch.int32))
+    return closed
+
+
+def socks_settle(received, pending: SockCalls, plans: dict[int, Plan | None], closed: torch.Tensor, ids=None,
+                 stack_limit: int = A.DEFAULT_STACK_LIMIT):
+    """settle() for many connections.  received: a Received, or (stream,
+    offsets, rows); ids as in socks_match_replies; closed: int32 [nsocks]
+    (closed_socks()).  Returns (stats, results, pending2, old_of_new): stats
+    in the caller's positions -- a call without a reply is RPCS_NETWORK_ERROR
+    on a closed socket and RPCS_PENDING on an open one --, results as
+    decode_results gives them, pending2 every calls_ for the next round (the
+    answered calls and those of closed sockets retired, `last` unchanged),
+    old_of_new int64 [count] the old caller position of call p of pending2."""
+    if isinstance(received, Received):
+        stream_bytes, offsets, rows = received.stream, received.offsets, received.conn_of
+    else:
+        stream_bytes, offsets, rows = received
+    dev, nc = pending.device, pending.ncalls
+    hdrs, tcall, treply = _socks_match_t(stream_bytes, offsets, rows, pending, ids)
+    _verify_results_t(stream_bytes, hdrs, tcall, pending, plans, stack_limit)
+    results = {}
+    for res in sorted(plans):
+        data, offs, index = _gather_results_t(stream_bytes, hdrs, tcall, pending, res)
+        if plans[res] is None:
+            results[res] = (index, None, None)
+        elif index.numel() == 0:
+            results[res] = (index, torch.empty(0, dtype=torch.uint8, device=dev), None)
+        else:
+            native, heap = Marshaler(plans[res], dev).decode(data, index.numel(), offs, stack_limit)
+            results[res] = (index, native, heap)
+    closed = closed.to(device=dev, dtype=torch.int32).contiguous()
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    stats = torch.empty(max(nc, 1), dtype=torch.int64, device=dev)[:nc]
+    kept = torch.empty(max(nc, 1), dtype=torch.int64, device=dev)[:nc]
+    kept_sock = torch.empty(max(nc, 1), dtype=torch.int32, device=dev)[:nc]
+    kept_pos = torch.empty(max(nc, 1), dtype=torch.int64, device=dev)[:nc]
+    ws = torch.empty(max(A.lib().xdrg_rpc_socks_pending_retire_workspace_size(nc), 16), dtype=torch.uint8, device=dev)
+    launch_socks_call_stats(hdrs, treply, pending, closed, stats)
+    launch_socks_pending_retire(pending, treply, closed, kept, kept_sock, kept_pos, count, ws)
+    if nc == 0:
+        e = torch.empty(0, dtype=torch.int64, device=dev)
+        return stats, results, SockCalls.from_device(kept, kept_sock, e, pending.last), e.clone()
+    pos = kept_pos[pending.inv]  # a survivor's new table position, by old caller position
+    alive = pos >= 0
+    rank = torch.cumsum(alive, 0) - 1
+    k = int(count.item())
+    slot = torch.empty(k + 1, dtype=torch.int64, device=dev)
+    slot.scatter_(0, torch.where(alive, rank, k), torch.arange(nc, dtype=torch.int64, device=dev))
+    old_of_new = slot[:k]
+    pending2 = SockCalls.from_device(kept[:k], kept_sock[:k], pos[old_of_new], pending.last)
+    return stats[pending.inv], results, pending2, old_of_new
