@@ -1,5 +1,5 @@
 // What the RPC batch stages share (verify_kernels.h, replies_kernels.h,
-// reply_batch_kernels.h, call_batch_kernels.h, settle_kernels.h).  Every stage
+// reply_batch_kernels.h, call_batch_kernels.h, pending_kernels.h).  Every stage
 // is count -> scan -> emit over 256-item tiles:
 //
 //   tile_reduce    a workgroup's 256 lanes to one sum and one count per tile

@@ -38,9 +38,9 @@ int xdrg_rpc_next_xids(const xdrg_rpc_call *d_calls, uint64_t ncalls, uint32_t l
   if ((ncalls && !d_calls) || (n && !d_xids)) return XDRG_EINVAL;
   if (misaligned(d_calls, 7) || misaligned(d_xids, 3)) return XDRG_EALIGN;
   if (n == 0) return XDRG_OK;
-  const uint64_t nb = (n + kCbThreads - 1) / kCbThreads;
-  k_cb_next_xids<<<uint32_t(nb), kCbThreads, 0, static_cast<hipStream_t>(stream)>>>(d_calls, ncalls, last_xid, n,
-                                                                                  d_xids);
+  const uint64_t nb = (n + kPendingThreads - 1) / kPendingThreads;
+  k_cb_next_xids<<<uint32_t(nb), kPendingThreads, 0, static_cast<hipStream_t>(stream)>>>(d_calls, ncalls, last_xid,
+                                                                                       n, d_xids);
   HIPCHK(hipGetLastError());
   return XDRG_OK;
 }
@@ -118,10 +118,10 @@ int xdrg_rpc_pending_add(const xdrg_rpc_call *d_calls, uint64_t ncalls, const xd
       misaligned(d_new_pos, 7))
     return XDRG_EALIGN;
   if (total == 0) return XDRG_OK;
-  const uint64_t nb = (total + kCbThreads - 1) / kCbThreads;
+  const uint64_t nb = (total + kPendingThreads - 1) / kPendingThreads;
   if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-  k_cb_pending_add<<<uint32_t(nb), kCbThreads, 0, static_cast<hipStream_t>(stream)>>>(d_calls, ncalls, d_new, n,
-                                                                                   d_merged, d_old_pos, d_new_pos);
+  k_cb_pending_add<<<uint32_t(nb), kPendingThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      d_calls, ncalls, d_new, n, d_merged, d_old_pos, d_new_pos);
   HIPCHK(hipGetLastError());
   return XDRG_OK;
 }

@@ -8,6 +8,7 @@
 //
 //   k_cb_next_xids    one lane per xid: the (k+1)-th value after last_xid that
 //                     is not pending, by two binary searches of the table
+//                     (pending_kernels.h)
 //   k_owner_fill, k_src_claim<cb_usable>   the lowest usable entry that names
 //                     a position owns it (batch_kernels.h)
 //   k_cb_sizes        one lane per position: its message bytes (44 + L with a
@@ -22,13 +23,13 @@
 //                     bytes from the winning source.
 //   k_cb_pending_add  one lane per old and per new entry of the pending table:
 //                     its place in the merged table by binary searches
+//                     (pending_kernels.h)
 #pragma once
-#include "batch_kernels.h"
+#include "pending_kernels.h"
 
 namespace xdrg {
 namespace dev {
 
-constexpr uint32_t kCbThreads = 256;
 constexpr uint32_t kCbHdrWords = 11;  // mark + the call header (arpc.h:44-48: xid, CALL, 2, prog, vers, proc, cred, verf)
 
 // What the sizes need of a source: how long a winning entry is.
@@ -60,79 +61,39 @@ struct cb_usable {
   __device__ __forceinline__ bool operator()(uint64_t) const { return true; }
 };
 
-// ------------------------------------------------------------- next xids
-// The entries of the sorted table whose xid is below x.
-__device__ __forceinline__ uint64_t cb_lower_bound(const xdrg_rpc_call *__restrict__ calls, uint64_t ncalls,
-                                                   uint32_t x) {
-  uint64_t lo = 0, hi = ncalls;
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (calls[mid].xid < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// rpc_sock::get_xid() n times, each followed by send_call (msgsock.h:118-122).
-// In rotated coordinates r(x) = (x - last - 1) mod 2^32 the table, read from
-// its split point s = lower_bound(last + 1) on and around its end, is
-// ascending: R[0] < R[1] < ...  The k-th free value is k + j for the smallest
-// j with R[j] - j > k (j pending values lie at or below it); j = ncalls when
-// there is none.  ncalls + n <= 2^32 - 1, so the value exists.
-__global__ __launch_bounds__(kCbThreads) void k_cb_next_xids(const xdrg_rpc_call *__restrict__ calls,
-                                                             uint64_t ncalls, uint32_t last, uint64_t n,
-                                                             uint32_t *__restrict__ xids) {
-  const uint64_t k = static_cast<uint64_t>(blockIdx.x) * kCbThreads + threadIdx.x;
+// ---------------------------------------------- next xids, pending add
+// rpc_sock::get_xid() n times, each followed by send_call (msgsock.h:118-122):
+// pt_nth_free on the whole table.
+__global__ __launch_bounds__(kPendingThreads) void k_cb_next_xids(const xdrg_rpc_call *__restrict__ calls,
+                                                                  uint64_t ncalls, uint32_t last, uint64_t n,
+                                                                  uint32_t *__restrict__ xids) {
+  const uint64_t k = static_cast<uint64_t>(blockIdx.x) * kPendingThreads + threadIdx.x;
   if (k >= n) return;
-  const uint32_t base = last + 1u;
-  const uint64_t s = cb_lower_bound(calls, ncalls, base);
-  uint64_t lo = 0, hi = ncalls;
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    const uint64_t at = s + mid < ncalls ? s + mid : s + mid - ncalls;
-    const uint64_t r = static_cast<uint32_t>(calls[at].xid - base);
-    // r >= mid in a table that keeps the contract; a signed compare keeps a
-    // broken one from wrapping
-    if (static_cast<int64_t>(r) - static_cast<int64_t>(mid) > static_cast<int64_t>(k)) hi = mid; else lo = mid + 1;
-  }
-  xids[k] = base + static_cast<uint32_t>(k) + static_cast<uint32_t>(lo);
-}
-
-// ----------------------------------------------------------- pending add
-// The first entry of d_new past the wrap: the smallest k with xid_k < xid_0
-// (n when the xids did not wrap).
-__device__ __forceinline__ uint64_t cb_wrap_point(const xdrg_rpc_call *__restrict__ fresh, uint64_t n) {
-  const uint32_t x0 = fresh[0].xid;
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (fresh[mid].xid >= x0) lo = mid + 1; else hi = mid;
-  }
-  return lo;
+  xids[k] = pt_nth_free(calls, ncalls, last, k);
 }
 
 // calls_ after the sends: lanes 0..ncalls-1 place the old entries, the next n
 // the new ones.  Every position written is below ncalls + n whatever the
 // arrays hold (a lower bound is at most its array's length).
-__global__ __launch_bounds__(kCbThreads) void k_cb_pending_add(const xdrg_rpc_call *__restrict__ calls,
-                                                               uint64_t ncalls,
-                                                               const xdrg_rpc_call *__restrict__ fresh, uint64_t n,
-                                                               xdrg_rpc_call *__restrict__ merged,
-                                                               uint64_t *__restrict__ old_pos,
-                                                               uint64_t *__restrict__ new_pos) {
-  const uint64_t t = static_cast<uint64_t>(blockIdx.x) * kCbThreads + threadIdx.x;
+__global__ __launch_bounds__(kPendingThreads) void k_cb_pending_add(const xdrg_rpc_call *__restrict__ calls,
+                                                                    uint64_t ncalls,
+                                                                    const xdrg_rpc_call *__restrict__ fresh,
+                                                                    uint64_t n, xdrg_rpc_call *__restrict__ merged,
+                                                                    uint64_t *__restrict__ old_pos,
+                                                                    uint64_t *__restrict__ new_pos) {
+  const uint64_t t = static_cast<uint64_t>(blockIdx.x) * kPendingThreads + threadIdx.x;
   if (t >= ncalls + n) return;
-  const uint64_t w = n ? cb_wrap_point(fresh, n) : 0u;
+  const uint64_t w = n ? pt_wrap_point(fresh, n) : 0u;
   if (t < ncalls) {
     const xdrg_rpc_call c = calls[t];
-    // the new entries below it: in the run before the wrap and in the one after
-    const uint64_t below = cb_lower_bound(fresh, w, c.xid) + cb_lower_bound(fresh + w, n - w, c.xid);
+    const uint64_t below = pt_fresh_below(fresh, n, w, c.xid);
     merged[t + below] = c;
     if (old_pos) old_pos[t] = t + below;
   } else {
     const uint64_t k = t - ncalls;
     const xdrg_rpc_call c = fresh[k];
     const uint64_t rank = k < w ? (n - w) + k : k - w;
-    const uint64_t at = cb_lower_bound(calls, ncalls, c.xid) + rank;
+    const uint64_t at = pt_lower_bound(calls, ncalls, c.xid) + rank;
     merged[at] = c;
     if (new_pos) new_pos[k] = at;
   }

@@ -16,6 +16,7 @@
 // capture") and keeps no state.
 #include <hip/hip_runtime.h>
 
+#include "pending_host.h"
 #include "replies_kernels.h"
 #include "verify_host.h"
 
@@ -33,20 +34,11 @@ int xdrg_rpc_match_replies(const void *d_stream, uint64_t len, const uint64_t *d
   if (misaligned(d_stream, 3) || misaligned(d_offsets, 7) || misaligned(d_calls, 7) || misaligned(d_hdrs, 15) ||
       misaligned(d_call, 7) || misaligned(d_reply_of, 7))
     return XDRG_EALIGN;
-  if (n == 0 && ncalls == 0) return XDRG_OK;
-  const uint64_t nb = (n + kReplyThreads - 1) / kReplyThreads;
-  if (nb > 0x7fffffffull || ncalls > 0x7fffffffffffull) return XDRG_EUNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (ncalls) HIPCHK(static_cast<hipError_t>(fill32(d_reply_of, 0xffffffffu, 2 * ncalls, stream)));
-  if (n == 0) return XDRG_OK;
-  auto *call = reinterpret_cast<unsigned long long *>(d_call);
-  auto *reply_of = reinterpret_cast<unsigned long long *>(d_reply_of);
-  k_reply_claim<<<uint32_t(nb), kReplyThreads, 0, s>>>(static_cast<const uint8_t *>(d_stream), len, d_offsets, n,
-                                                       d_calls, ncalls, call, reply_of);
-  HIPCHK(hipGetLastError());
-  k_reply_resolve<<<uint32_t(nb), kReplyThreads, 0, s>>>(d_hdrs, n, call, reply_of);
-  HIPCHK(hipGetLastError());
-  return XDRG_OK;
+  return launch_match(n, ncalls, d_hdrs, d_call, d_reply_of, stream,
+                      [&](uint32_t nb, hipStream_t s, unsigned long long *call, unsigned long long *reply_of) {
+                        k_reply_claim<<<nb, kPendingThreads, 0, s>>>(static_cast<const uint8_t *>(d_stream), len,
+                                                                     d_offsets, n, d_calls, ncalls, call, reply_of);
+                      });
 }
 
 int xdrg_rpc_verify_results(const void *d_stream, uint64_t len, xdrg_rpc_hdr *d_hdrs, const uint64_t *d_call,

@@ -4,7 +4,8 @@
 // xid, its result verified with that call's result type, and the results of
 // one type gathered for xdrg_decode.
 //
-//   k_reply_claim / k_reply_resolve   rpc_sock::recv_msg for every message:
+//   k_reply_claim / k_pending_resolve   rpc_sock::recv_msg for every message
+//       (the steps are pending_kernels.h's, here on the whole table):
 //       the message's own xid (word 0) and msg_type (word 1) are read, a
 //       REPLY's xid is looked up in the pending table (sorted by xid,
 //       unsigned: rpc_sock::calls_) by binary search, and the lowest message
@@ -18,80 +19,25 @@
 //       g.done(), and GARBAGE_RES for the reply that throws (arpc.h:87-89).
 //   gather_res_key   one result type's bytes as an indexed stream: the
 //       selector of verify_kernels.h's k_gather_count / k_gather_emit.
-//
-// A header is rewritten through its first 16 bytes (xid, action | err |
-// mtype, w[0], w[1]): one 16-byte load, one 16-byte store when it changes.
 #pragma once
+#include "pending_kernels.h"
 #include "verify_kernels.h"
 
 namespace xdrg {
 namespace dev {
 
-constexpr unsigned long long kNoCall = XDRG_RPC_NO_CALL;
-// d_call between the two match kernels: a REPLY whose xid is in no entry
-constexpr unsigned long long kUnknownCall = XDRG_RPC_NO_CALL - 1u;
-constexpr uint32_t kMsgReply = 1;  // msg_type REPLY (rpc_msg.x)
-constexpr uint32_t kReplyThreads = 256;
-
-// The first 16 bytes of a header: action in the low half of word 1, err in
-// bits 16-23.
-__device__ __forceinline__ uint32_t hdr_action(const u32x4 &q) { return q.y & 0xffffu; }
-__device__ __forceinline__ uint32_t hdr_err(const u32x4 &q) { return (q.y >> 16) & 0xffu; }
-__device__ __forceinline__ void hdr_set(u32x4 &q, uint32_t action, uint32_t err) {
-  q.y = (q.y & 0xff000000u) | ((err & 0xffu) << 16) | action;
-}
-__device__ __forceinline__ u32x4 *hdr_head(xdrg_rpc_hdr *h) { return reinterpret_cast<u32x4 *>(h); }
-
-// The entry of the sorted table with this xid, or ncalls.  Stays inside
-// [0, ncalls) whatever the table holds.
-__device__ __forceinline__ uint64_t find_call(const xdrg_rpc_call *__restrict__ calls, uint64_t ncalls,
-                                              uint32_t xid) {
-  uint64_t lo = 0, hi = ncalls;
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (calls[mid].xid < xid) lo = mid + 1; else hi = mid;
-  }
-  return lo < ncalls && calls[lo].xid == xid ? lo : ncalls;
-}
-
 // One message per lane.  call[i] = the entry its xid names (claimed for the
 // lowest i by atomicMin), kUnknownCall for a REPLY to no entry, kNoCall for
-// everything that is no REPLY: a message shorter than xid + msg_type, a CALL,
-// another msg_type, or offsets that are no message of this stream (never
-// read).  reply_of[] was filled with kNoCall by the launch before this one.
-__global__ __launch_bounds__(kReplyThreads) void k_reply_claim(
+// everything that is no REPLY.  reply_of[] was filled with kNoCall by the
+// launch before this one.
+__global__ __launch_bounds__(kPendingThreads) void k_reply_claim(
     const uint8_t *__restrict__ s, uint64_t len, const uint64_t *__restrict__ offs, uint64_t n,
     const xdrg_rpc_call *__restrict__ calls, uint64_t ncalls, unsigned long long *__restrict__ call,
     unsigned long long *__restrict__ reply_of) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kReplyThreads + threadIdx.x;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kPendingThreads + threadIdx.x;
   if (i >= n) return;
-  const uint64_t m0 = offs[i], m1 = offs[i + 1];
-  unsigned long long c = kNoCall;
-  if (m1 <= len && m1 >= m0 && m1 - m0 >= 12u && !(m0 & 3u)) {
-    const uint32_t xid = bswap32(ld32(s + m0 + 4)), mtype = bswap32(ld32(s + m0 + 8));
-    if (mtype == kMsgReply) {
-      const uint64_t e = find_call(calls, ncalls, xid);
-      c = e < ncalls ? e : kUnknownCall;
-      if (e < ncalls) atomicMin(reply_of + e, static_cast<unsigned long long>(i));
-    }
-  }
-  call[i] = c;
-}
-
-// The compare: message i keeps entry c when it is the one that claimed it.
-__global__ __launch_bounds__(kReplyThreads) void k_reply_resolve(
-    xdrg_rpc_hdr *__restrict__ hdrs, uint64_t n, unsigned long long *__restrict__ call,
-    const unsigned long long *__restrict__ reply_of) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kReplyThreads + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long c = call[i];
-  if (c == kNoCall) return;
-  if (c != kUnknownCall && reply_of[c] == i) return;  // the call's first reply
-  u32x4 *hp = hdr_head(hdrs + i);
-  u32x4 q = *hp;
-  hdr_set(q, XDRG_RPCR_UNKNOWN_XID, hdr_err(q));
-  *hp = q;
-  call[i] = kNoCall;
+  uint32_t xid;
+  call[i] = reply_xid(s, len, offs, i, &xid) ? pt_claim(calls, ncalls, 0u, ncalls, xid, i, reply_of) : kNoCall;
 }
 
 // ------------------------------------------------------- result verdicts

@@ -1,4 +1,6 @@
-// Settling a reply batch on gfx950: the launchers of settle_kernels.h.
+// Settling a reply batch on gfx950: what the asynchronous client's pending
+// calls became, and calls_ after the erases (the kernels are
+// pending_kernels.h's, on one rpc_sock's whole table).
 //
 //   xdrg_rpc_call_stats      the call_result the callback of
 //                            asynchronous_client_base::invoke receives for
@@ -15,8 +17,7 @@
 // (no memset or memcpy nodes: xdrgpu.h "Graph capture") and keep no state.
 #include <hip/hip_runtime.h>
 
-#include "host_common.h"
-#include "settle_kernels.h"
+#include "pending_host.h"
 
 namespace {
 
@@ -25,9 +26,6 @@ using namespace xdrg::dev;
 using namespace xdrg::host;
 
 static_assert(sizeof(xdrg_rpc_call_stat) == 8, "xdrg_rpc_call_stat is 8 bytes");
-
-// the kept entries of every tile, one word each
-size_t st_ws_bytes(uint64_t ncalls) { return align256(tiles_of(ncalls) * 8); }
 
 }  // namespace
 
@@ -41,13 +39,13 @@ int xdrg_rpc_call_stats(const xdrg_rpc_hdr *d_hdrs, uint64_t n, const uint64_t *
   if (ncalls == 0) return XDRG_OK;
   const uint64_t nb = tiles_of(ncalls);
   if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-  k_st_call_stats<<<uint32_t(nb), kTileThreads, 0, static_cast<hipStream_t>(stream)>>>(d_hdrs, n, d_reply_of, ncalls,
-                                                                                   unanswered, d_stats);
+  k_st_call_stats<><<<uint32_t(nb), kTileThreads, 0, static_cast<hipStream_t>(stream)>>>(d_hdrs, n, d_reply_of, ncalls,
+                                                                                     unanswered, d_stats);
   HIPCHK(hipGetLastError());
   return XDRG_OK;
 }
 
-size_t xdrg_rpc_pending_retire_workspace_size(uint64_t ncalls) { return st_ws_bytes(ncalls); }
+size_t xdrg_rpc_pending_retire_workspace_size(uint64_t ncalls) { return retire_ws_bytes(ncalls); }
 
 int xdrg_rpc_pending_retire(const xdrg_rpc_call *d_calls, uint64_t ncalls, const uint64_t *d_reply_of,
                             xdrg_rpc_call *d_kept, uint64_t *d_kept_pos, uint64_t *d_count, void *d_workspace,
@@ -58,23 +56,14 @@ int xdrg_rpc_pending_retire(const xdrg_rpc_call *d_calls, uint64_t ncalls, const
   if (misaligned(d_calls, 7) || misaligned(d_reply_of, 7) || misaligned(d_kept, 7) || misaligned(d_kept_pos, 7) ||
       misaligned(d_count, 7) || misaligned(d_workspace, 7))
     return XDRG_EALIGN;
-  if (ncalls && (!d_workspace || workspace_bytes < st_ws_bytes(ncalls))) return XDRG_ESPACE;
-  const uint64_t nb = tiles_of(ncalls);
-  if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  auto *tiles = static_cast<unsigned long long *>(d_workspace);
-  if (nb) {
-    k_st_count<<<uint32_t(nb), kTileThreads, 0, s>>>(d_reply_of, ncalls, tiles);
-    HIPCHK(hipGetLastError());
-  }
-  k_tile_scan<1, 1><<<1, kScanThreads, 0, s>>>(tiles, nullptr, nb, count_total{d_count});  // nb == 0: the count alone
-  HIPCHK(hipGetLastError());
-  if (nb) {
-    k_st_scatter<<<uint32_t(nb), kTileThreads, 0, s>>>(d_calls, ncalls, d_reply_of, tiles, d_kept, d_kept_pos);
-    HIPCHK(hipGetLastError());
-  }
-  return XDRG_OK;
+  return launch_retire(
+      ncalls, d_count, d_workspace, workspace_bytes, stream,
+      [&](uint32_t nb, hipStream_t s, unsigned long long *tiles) {
+        k_st_count<><<<nb, kTileThreads, 0, s>>>(d_reply_of, ncalls, tiles);
+      },
+      [&](uint32_t nb, hipStream_t s, unsigned long long *tiles) {
+        k_st_scatter<><<<nb, kTileThreads, 0, s>>>(d_calls, ncalls, d_reply_of, tiles, d_kept, d_kept_pos);
+      });
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 // memset or memcpy nodes: xdrgpu.h "Graph capture") and keep no state.
 #include <hip/hip_runtime.h>
 
-#include "host_common.h"
+#include "pending_host.h"
 #include "socks_kernels.h"
 
 namespace {
@@ -26,9 +26,6 @@ namespace {
 using namespace xdrg;
 using namespace xdrg::dev;
 using namespace xdrg::host;
-
-// the kept entries of every tile, one word each (as settle.hip)
-size_t sk_ws_bytes(uint64_t ncalls) { return align256(tiles_of(ncalls) * 8); }
 
 }  // namespace
 
@@ -48,8 +45,8 @@ int xdrg_rpc_socks_next_xids(const xdrg_rpc_call *d_calls, const uint32_t *d_soc
     return XDRG_EALIGN;
   const uint64_t lanes = n + (d_last_out ? nsocks : 0u);
   if (lanes == 0) return XDRG_OK;
-  const uint64_t nb = (lanes + kSkThreads - 1) / kSkThreads;
-  k_sk_next_xids<<<uint32_t(nb), kSkThreads, 0, static_cast<hipStream_t>(stream)>>>(
+  const uint64_t nb = (lanes + kPendingThreads - 1) / kPendingThreads;
+  k_sk_next_xids<<<uint32_t(nb), kPendingThreads, 0, static_cast<hipStream_t>(stream)>>>(
       d_calls, d_sock, ncalls, d_last, nsocks, d_call_sock, n, d_xids, d_last_out);
   HIPCHK(hipGetLastError());
   return XDRG_OK;
@@ -75,9 +72,9 @@ int xdrg_rpc_socks_pending_add(const xdrg_rpc_call *d_calls, const uint32_t *d_s
       misaligned(d_new_pos, 7) || misaligned(d_sock, 3) || misaligned(d_new_sock, 3) || misaligned(d_merged_sock, 3))
     return XDRG_EALIGN;
   if (total == 0) return XDRG_OK;
-  const uint64_t nb = (total + kSkThreads - 1) / kSkThreads;
+  const uint64_t nb = (total + kPendingThreads - 1) / kPendingThreads;
   if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-  k_sk_pending_add<<<uint32_t(nb), kSkThreads, 0, static_cast<hipStream_t>(stream)>>>(
+  k_sk_pending_add<<<uint32_t(nb), kPendingThreads, 0, static_cast<hipStream_t>(stream)>>>(
       d_calls, d_sock, ncalls, d_new, d_new_sock, n, d_merged, d_merged_sock, d_old_pos, d_new_pos);
   HIPCHK(hipGetLastError());
   return XDRG_OK;
@@ -93,20 +90,12 @@ int xdrg_rpc_socks_match_replies(const void *d_stream, uint64_t len, const uint6
       misaligned(d_call, 7) || misaligned(d_reply_of, 7) || misaligned(d_msg_row, 3) || misaligned(d_row_sock, 3) ||
       misaligned(d_sock, 3))
     return XDRG_EALIGN;
-  if (n == 0 && ncalls == 0) return XDRG_OK;
-  const uint64_t nb = (n + kSkThreads - 1) / kSkThreads;
-  if (nb > 0x7fffffffull || ncalls > 0x7fffffffffffull) return XDRG_EUNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (ncalls) HIPCHK(static_cast<hipError_t>(fill32(d_reply_of, 0xffffffffu, 2 * ncalls, stream)));
-  if (n == 0) return XDRG_OK;
-  auto *call = reinterpret_cast<unsigned long long *>(d_call);
-  auto *reply_of = reinterpret_cast<unsigned long long *>(d_reply_of);
-  k_sk_claim<<<uint32_t(nb), kSkThreads, 0, s>>>(static_cast<const uint8_t *>(d_stream), len, d_offsets, n, d_msg_row,
-                                                 d_row_sock, nrows, d_calls, d_sock, ncalls, call, reply_of);
-  HIPCHK(hipGetLastError());
-  k_sk_resolve<<<uint32_t(nb), kSkThreads, 0, s>>>(d_hdrs, n, call, reply_of);
-  HIPCHK(hipGetLastError());
-  return XDRG_OK;
+  return launch_match(n, ncalls, d_hdrs, d_call, d_reply_of, stream,
+                      [&](uint32_t nb, hipStream_t s, unsigned long long *call, unsigned long long *reply_of) {
+                        k_sk_claim<<<nb, kPendingThreads, 0, s>>>(static_cast<const uint8_t *>(d_stream), len,
+                                                                  d_offsets, n, d_msg_row, d_row_sock, nrows, d_calls,
+                                                                  d_sock, ncalls, call, reply_of);
+                      });
 }
 
 int xdrg_rpc_socks_call_stats(const xdrg_rpc_hdr *d_hdrs, uint64_t n, const uint64_t *d_reply_of,
@@ -125,7 +114,7 @@ int xdrg_rpc_socks_call_stats(const xdrg_rpc_hdr *d_hdrs, uint64_t n, const uint
   return XDRG_OK;
 }
 
-size_t xdrg_rpc_socks_pending_retire_workspace_size(uint64_t ncalls) { return sk_ws_bytes(ncalls); }
+size_t xdrg_rpc_socks_pending_retire_workspace_size(uint64_t ncalls) { return retire_ws_bytes(ncalls); }
 
 int xdrg_rpc_socks_pending_retire(const xdrg_rpc_call *d_calls, const uint32_t *d_sock, uint64_t ncalls,
                                   const uint64_t *d_reply_of, const uint32_t *d_closed, uint64_t nsocks,
@@ -142,24 +131,15 @@ int xdrg_rpc_socks_pending_retire(const xdrg_rpc_call *d_calls, const uint32_t *
       misaligned(d_count, 7) || misaligned(d_workspace, 7) || misaligned(d_sock, 3) || misaligned(d_closed, 3) ||
       misaligned(d_kept_sock, 3))
     return XDRG_EALIGN;
-  if (ncalls && (!d_workspace || workspace_bytes < sk_ws_bytes(ncalls))) return XDRG_ESPACE;
-  const uint64_t nb = tiles_of(ncalls);
-  if (nb > 0x7fffffffull) return XDRG_EUNSUPPORTED;
-
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  auto *tiles = static_cast<unsigned long long *>(d_workspace);
-  if (nb) {
-    k_sk_count<<<uint32_t(nb), kTileThreads, 0, s>>>(d_reply_of, d_sock, ncalls, d_closed, nsocks, tiles);
-    HIPCHK(hipGetLastError());
-  }
-  k_tile_scan<1, 1><<<1, kScanThreads, 0, s>>>(tiles, nullptr, nb, count_total{d_count});  // nb == 0: the count alone
-  HIPCHK(hipGetLastError());
-  if (nb) {
-    k_sk_scatter<<<uint32_t(nb), kTileThreads, 0, s>>>(d_calls, d_sock, ncalls, d_reply_of, d_closed, nsocks, tiles,
-                                                      d_kept, d_kept_sock, d_kept_pos);
-    HIPCHK(hipGetLastError());
-  }
-  return XDRG_OK;
+  return launch_retire(
+      ncalls, d_count, d_workspace, workspace_bytes, stream,
+      [&](uint32_t nb, hipStream_t s, unsigned long long *tiles) {
+        k_sk_count<<<nb, kTileThreads, 0, s>>>(d_reply_of, d_sock, ncalls, d_closed, nsocks, tiles);
+      },
+      [&](uint32_t nb, hipStream_t s, unsigned long long *tiles) {
+        k_sk_scatter<<<nb, kTileThreads, 0, s>>>(d_calls, d_sock, ncalls, d_reply_of, d_closed, nsocks, tiles, d_kept,
+                                                 d_kept_sock, d_kept_pos);
+      });
 }
 
 }  // extern "C"

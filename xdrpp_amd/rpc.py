@@ -457,54 +457,31 @@ def call_type(args: XdrType | None = None, name: str = "rpc_call") -> Struct:
     return Struct(name, fields)
 
 
-class PendingCalls:
-    """rpc_sock::calls_ (msgsock.h) for a batch: the outstanding calls keyed
-    by xid, each with `res`, the number of its result type.  Sorts by xid as
-    unsigned (the table xdrg_rpc_match_replies searches), raises ValueError on
-    a duplicate xid, and keeps the device table and the permutation, so that
-    everything the functions below take and return names a call by its
-    position in `xids`.  last_xid: rpc_sock::xid_, the last xid handed out (0
-    in a fresh rpc_sock); call_batch() counts on from it."""
+class _CallTable:
+    """What PendingCalls and SockCalls keep: `table` (xdrg_rpc_call records
+    int64 [ncalls], sorted), `perm` (table position -> the caller's) and `inv`
+    (the caller's -> table position), all on the device."""
 
-    def __init__(self, xids, res, device="cuda", *, last_xid: int = 0):
-        if isinstance(xids, torch.Tensor):
-            xids = xids.cpu().numpy()
-        if isinstance(res, torch.Tensor):
-            res = res.cpu().numpy()
-        x = (np.asarray(xids).astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32)
-        r = np.broadcast_to(np.asarray(res).astype(np.int64) & 0xFFFFFFFF, x.shape).astype(np.uint32)
-        order = np.argsort(x, kind="stable")
-        xs = x[order]
-        if np.any(xs[1:] == xs[:-1]):
-            raise ValueError("PendingCalls: duplicate xid")
-        t = np.empty(x.size, dtype=CALL_DTYPE)
-        t["xid"], t["res"] = xs, r[order]
-        inv = np.empty(x.size, dtype=np.int64)
-        inv[order] = np.arange(x.size, dtype=np.int64)
+    def _from_host(self, order: np.ndarray, xids: np.ndarray, res: np.ndarray, device) -> None:
+        """The caller's uint32 xids and res, and the order that sorts them."""
+        t = np.empty(order.size, dtype=CALL_DTYPE)
+        t["xid"], t["res"] = xids[order], res[order]
+        inv = np.empty(order.size, dtype=np.int64)
+        inv[order] = np.arange(order.size, dtype=np.int64)
         self.device = torch.device(device)
-        self.ncalls = int(x.size)
-        self.last_xid = int(last_xid) & 0xFFFFFFFF
-        self._calls = t                                                 # host copy, sorted
-        self.table = torch.from_numpy(t.view(np.int64).copy()).to(self.device)  # xdrg_rpc_call [ncalls]
-        self.perm = torch.from_numpy(order.astype(np.int64)).to(self.device)    # table position -> caller's
-        self.inv = torch.from_numpy(inv).to(self.device)                        # caller's -> table position
+        self.ncalls = int(order.size)
+        self._calls = t  # host copy, sorted
+        self.table = torch.from_numpy(t.view(np.int64).copy()).to(self.device)
+        self.perm = torch.from_numpy(order.astype(np.int64)).to(self.device)
+        self.inv = torch.from_numpy(inv).to(self.device)
 
-    @classmethod
-    def from_device(cls, table: torch.Tensor, inv: torch.Tensor, *, last_xid: int = 0) -> "PendingCalls":
-        """A table that is on the device already, without a host sort: `table`
-        int64 [ncalls], xdrg_rpc_call records sorted by xid as unsigned with
-        no duplicates (xdrg_rpc_pending_add's d_merged; not checked), `inv`
-        int64 [ncalls], the table position of the caller's call c (its
-        d_old_pos / d_new_pos)."""
-        self = cls.__new__(cls)
+    def _from_device(self, table: torch.Tensor, inv: torch.Tensor) -> None:
         self.device = table.device
         self.ncalls = int(table.numel())
-        self.last_xid = int(last_xid) & 0xFFFFFFFF
         self._calls = None
         self.table, self.inv = table, inv
         self.perm = torch.empty_like(inv)
         self.perm[inv] = torch.arange(self.ncalls, dtype=torch.int64, device=self.device)
-        return self
 
     @property
     def calls(self) -> np.ndarray:
@@ -524,6 +501,44 @@ class PendingCalls:
         if self.ncalls == 0:
             return call
         return torch.where(call >= 0, self.inv[call.clamp(min=0)], call)
+
+
+def _as_u32(v, shape=None) -> np.ndarray:
+    """Integers of the host or the device as uint32 (mod 2^32), flat or broadcast to `shape`."""
+    v = (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.int64) & 0xFFFFFFFF
+    return (v.reshape(-1) if shape is None else np.broadcast_to(v, shape)).astype(np.uint32)
+
+
+class PendingCalls(_CallTable):
+    """rpc_sock::calls_ (msgsock.h) for a batch: the outstanding calls keyed
+    by xid, each with `res`, the number of its result type.  Sorts by xid as
+    unsigned (the table xdrg_rpc_match_replies searches), raises ValueError on
+    a duplicate xid, and keeps the device table and the permutation, so that
+    everything the functions below take and return names a call by its
+    position in `xids`.  last_xid: rpc_sock::xid_, the last xid handed out (0
+    in a fresh rpc_sock); call_batch() counts on from it."""
+
+    def __init__(self, xids, res, device="cuda", *, last_xid: int = 0):
+        x = _as_u32(xids)
+        r = _as_u32(res, x.shape)
+        order = np.argsort(x, kind="stable")
+        xs = x[order]
+        if np.any(xs[1:] == xs[:-1]):
+            raise ValueError("PendingCalls: duplicate xid")
+        self._from_host(order, x, r, device)
+        self.last_xid = int(last_xid) & 0xFFFFFFFF
+
+    @classmethod
+    def from_device(cls, table: torch.Tensor, inv: torch.Tensor, *, last_xid: int = 0) -> "PendingCalls":
+        """A table that is on the device already, without a host sort: `table`
+        int64 [ncalls], xdrg_rpc_call records sorted by xid as unsigned with
+        no duplicates (xdrg_rpc_pending_add's d_merged; not checked), `inv`
+        int64 [ncalls], the table position of the caller's call c (its
+        d_old_pos / d_new_pos)."""
+        self = cls.__new__(cls)
+        self._from_device(table, inv)
+        self.last_xid = int(last_xid) & 0xFFFFFFFF
+        return self
 
     def retire(self, reply_of: torch.Tensor) -> tuple["PendingCalls", torch.Tensor]:
         """calls_ after the erases of a reply batch (recv_msg, msgsock.cc:
@@ -1103,7 +1118,7 @@ class Receiver:
 
 
 # --------------------------------- the asynchronous client, many connections
-class SockCalls:
+class SockCalls(_CallTable):
     """The calls_ of many rpc_socks in one table (include/xdrgpu.h "The
     asynchronous client over many connections"): every outstanding call is
     keyed by (sock, xid), `table` (xdrg_rpc_call records) and `sock` (int32
@@ -1112,13 +1127,15 @@ class SockCalls:
     may both have xid 1 pending; a duplicate (sock, xid) raises ValueError.  As
     PendingCalls does, it keeps the permutation, so that everything the
     functions below take and return names a call by its position in `xids`;
-    verify_results and gather_results take it as they take a PendingCalls."""
+    verify_results and gather_results take it as they take a PendingCalls.
+    `calls` is a cached host copy (the array sorted here, or one download of a
+    device-built table), not a fresh read of the device: do not write to it."""
 
     def __init__(self, socks, xids, res, nsocks: int | None = None, device="cuda", *, last=None):
         as_np = lambda v: v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-        x = (as_np(xids).astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32)
+        x = _as_u32(xids)
         g = np.broadcast_to(as_np(socks).astype(np.int64), x.shape).astype(np.int64)
-        r = np.broadcast_to(as_np(res).astype(np.int64) & 0xFFFFFFFF, x.shape).astype(np.uint32)
+        r = _as_u32(res, x.shape)
         if nsocks is None:
             nsocks = int(g.max()) + 1 if g.size else (0 if last is None else len(as_np(last).reshape(-1)))
         if g.size and (g.min() < 0 or g.max() >= nsocks):
@@ -1127,19 +1144,11 @@ class SockCalls:
         gs, xs = g[order], x[order]
         if np.any((gs[1:] == gs[:-1]) & (xs[1:] == xs[:-1])):
             raise ValueError("SockCalls: duplicate (sock, xid)")
-        t = np.empty(x.size, dtype=CALL_DTYPE)
-        t["xid"], t["res"] = xs, r[order]
-        inv = np.empty(x.size, dtype=np.int64)
-        inv[order] = np.arange(x.size, dtype=np.int64)
-        lv = np.zeros(nsocks, dtype=np.int64) if last is None else \
-            np.broadcast_to(as_np(last).astype(np.int64) & 0xFFFFFFFF, (nsocks,))
-        self.device = torch.device(device)
-        self.ncalls, self.nsocks = int(x.size), int(nsocks)
-        self.table = torch.from_numpy(t.view(np.int64).copy()).to(self.device)
+        self._from_host(order, x, r, device)
+        self.nsocks = int(nsocks)
         self.sock = torch.from_numpy(gs.astype(np.int32)).to(self.device)
-        self.last = torch.from_numpy(lv.astype(np.uint32).view(np.int32).copy()).to(self.device)
-        self.perm = torch.from_numpy(order.astype(np.int64)).to(self.device)
-        self.inv = torch.from_numpy(inv).to(self.device)
+        lv = np.zeros(nsocks, dtype=np.uint32) if last is None else _as_u32(last, (nsocks,))
+        self.last = torch.from_numpy(lv.view(np.int32).copy()).to(self.device)
 
     @classmethod
     def from_device(cls, table: torch.Tensor, sock: torch.Tensor, inv: torch.Tensor,
@@ -1149,20 +1158,9 @@ class SockCalls:
         d_kept_sock; not checked), `inv` int64 [ncalls] the table position of
         the caller's call c, `last` int32 [nsocks]."""
         self = cls.__new__(cls)
-        self.device = table.device
-        self.ncalls, self.nsocks = int(table.numel()), int(last.numel())
-        self.table, self.sock, self.inv, self.last = table, sock, inv, last
-        self.perm = torch.empty_like(inv)
-        self.perm[inv] = torch.arange(self.ncalls, dtype=torch.int64, device=self.device)
+        self._from_device(table, inv)
+        self.nsocks, self.sock, self.last = int(last.numel()), sock, last
         return self
-
-    to_caller = PendingCalls.to_caller
-    to_table = PendingCalls.to_table
-
-    @property
-    def calls(self) -> np.ndarray:
-        """The sorted table on the host (copies)."""
-        return self.table.cpu().numpy().view(CALL_DTYPE).reshape(-1).copy()
 
     def socks_numpy(self) -> np.ndarray:
         """The socket of every table entry, on the host (copies)."""
