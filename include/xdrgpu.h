@@ -1416,6 +1416,109 @@ int xdrg_rpc_recv_batch(const void *d_buf, uint64_t buf_len,
                         xdrg_status *d_status, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* The send side                                                           */
+/* ---------------------------------------------------------------------- */
+/*
+ * msg_sock::putmsg (xdrpp/msgsock.cc:121-134) for the messages of many
+ * streams and many connections in one call: the step before writev.  The
+ * messages come as up to XDRG_RPC_MAX_SEND_SRCS sources, each a stream of
+ * record-marked messages (xdrg_rpc_reply_batch's, xdrg_rpc_call_batch's,
+ * xdrg_rpc_recv_batch's d_out) with its offsets and the connection of every
+ * entry, in any order: the replies of an asynchronous service in completion
+ * order (arpc.h:102-200), calls in application order, a reply stream and a
+ * call stream for the same connections (rpc_sock, msgsock.cc:202-232).  They
+ * leave as one stream in which every connection's messages are contiguous and
+ * in putmsg order, with one queue record per connection: what wqueue_ and
+ * wsize_ of a fresh queue would hold, ready for one writev per connection.
+ *
+ * Order.  Entry k of source s has the global number g = (count_cap of the
+ * sources before s) + k; entries at or past min(*d_count, count_cap) of their
+ * source are not used.  putmsg order on a connection is ascending g: source 0
+ * first, each source in entry order.  The queued messages are sorted by
+ * (connection, g), a stable sort whose result depends on the inputs only (no
+ * atomic decides a position), and written back to back in d_out.
+ *
+ * Outcomes.  Every used entry has exactly one, reported in d_pos[g] when d_pos
+ * is given (an unused entry reads -2 there and is not counted):
+ *   empty     d_offsets[k] == d_offsets[k + 1] (xdrg_rpc_reply_batch's "no
+ *             reply", xdrg_rpc_call_batch's "no message"): skipped, -2
+ *   unusable  -3: a span with end < begin or end > bytes_len, an offset or a
+ *             length that is not a multiple of 4, a length below 4 or above 4
+ *             + XDRG_MAX_MSG, a first word that is not BE((length - 4) |
+ *             XDRG_MARK_LAST), a connection at or past nconns.  Nothing of
+ *             d_bytes past the first word is read for it: what is written to a
+ *             socket is always well framed.
+ *   dropped   d_closed[conn] != 0, putmsg on a socket with wfail_
+ *             (msgsock.cc:124-127): -1
+ *   queued    d_pos[g] = its queue position j
+ *
+ * Outputs.  d_offsets[j] is the mark of queue position j; d_offsets[m],
+ * d_status->total_bytes and *d_count carry the totals (m messages).
+ * d_conn_of[j] is the connection of position j, d_from[j] = s << 32 | k where
+ * it came from.  d_queues[c] is written for every connection, also one with
+ * nothing queued (msgs 0, len 0, begin = the end of the connection before
+ * it): the ranges of consecutive connections tile the stream.  It depends on
+ * the sizes only, not on the copy.  d_counts = {queued, dropped, empty,
+ * unusable}, written by a kernel from tile sums.  Entries of d_offsets past m
+ * and of d_conn_of / d_from at or past m are unspecified.
+ *
+ * A capacity below the total is XDRG_ERR_OVERFLOW_PUT at the first queue
+ * position that does not fit (record = j, op 0xffff): every message before it
+ * is written as in an unbounded call, nothing at or past out_capacity is
+ * written, d_queues and d_offsets are complete and total_bytes is what the
+ * stream needs.
+ *
+ * Validated on the host before any HIP call.  XDRG_EINVAL: NULL d_offsets,
+ * d_count, d_status; NULL srcs with nsrcs > 0, d_out with out_capacity > 0,
+ * d_conn_of or d_from with entries > 0, d_queues with nconns > 0; nsrcs above
+ * the limit; a source with count_cap > 0 and NULL d_offsets, or with
+ * bytes_len > 0 and NULL d_bytes; d_out overlapping a source's bytes.
+ * XDRG_EALIGN: a u64 array, d_queues, d_status or the workspace not 8-aligned;
+ * d_out, d_bytes, d_conn, d_conn_of or d_closed not 4-aligned.
+ * XDRG_EUNSUPPORTED: entries (the sum of count_cap) above 0xffffffff or nconns
+ * above 0x7fffffff.  XDRG_ESPACE: workspace below
+ * xdrg_rpc_send_batch_workspace_size(entries, nconns), which need not be
+ * initialised.  Zero entries: d_offsets[0], the totals and every queue record
+ * are still written.
+ *
+ * Kernels only: no memset or memcpy node, no wait on the stream, no
+ * allocation, no state; capturable on one stream, and the launch sequence does
+ * not depend on what the device arrays hold (a batch that is already in
+ * connection order skips the sort on the device, not on the host).  Whatever
+ * the device arrays hold, nothing outside the given inputs is read and nothing
+ * outside the outputs written.  The sort works on XDRG_RPC_SEND_SORT_TILE
+ * entries a workgroup.
+ */
+typedef struct xdrg_rpc_send_src { /* 48 bytes */
+  const uint8_t  *d_bytes;   /* a stream of record-marked messages */
+  const uint64_t *d_offsets; /* count + 1: entry k = [d_offsets[k], d_offsets[k+1]) */
+  const uint32_t *d_conn;    /* count: the connection of entry k; NULL: every entry goes to `conn` */
+  const uint64_t *d_count;   /* device count; NULL: count_cap is the count */
+  uint64_t bytes_len;
+  uint32_t count_cap;        /* host bound, sizes the launch; min(*d_count, count_cap) entries are used */
+  uint32_t conn;
+} xdrg_rpc_send_src;
+#define XDRG_RPC_MAX_SEND_SRCS 64u
+#define XDRG_RPC_SEND_SORT_TILE 2048u
+
+typedef struct xdrg_rpc_wqueue { /* 32 bytes, one per connection, written for every connection */
+  uint64_t first;  /* queue position of its first message */
+  uint64_t msgs;   /* messages queued for it by this call */
+  uint64_t begin;  /* its bytes are d_out[begin, begin + len): wsize_ of a fresh queue */
+  uint64_t len;
+} xdrg_rpc_wqueue;
+
+size_t xdrg_rpc_send_batch_workspace_size(uint64_t entries /* sum of count_cap */, uint64_t nconns);
+int xdrg_rpc_send_batch(const xdrg_rpc_send_src *srcs /* HOST */, uint32_t nsrcs,
+                        uint64_t nconns, const uint32_t *d_closed /* nconns, or NULL: all open */,
+                        void *d_out, uint64_t out_capacity,
+                        uint64_t *d_offsets /* entries + 1 */, uint64_t *d_count,
+                        uint32_t *d_conn_of /* entries */, uint64_t *d_from /* entries: src << 32 | k */,
+                        int64_t *d_pos /* entries, source-major; may be NULL */,
+                        xdrg_rpc_wqueue *d_queues /* nconns */, uint64_t *d_counts /* 4, may be NULL */,
+                        void *d_workspace, size_t workspace_bytes, xdrg_status *d_status, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* The asynchronous client over many connections                           */
 /* ---------------------------------------------------------------------- */
 /*

@@ -149,6 +149,7 @@ EXPORTED = (
     "xdrg_rpc_recv_batch", "xdrg_rpc_recv_batch_workspace_size",
     "xdrg_rpc_socks_next_xids", "xdrg_rpc_socks_pending_add", "xdrg_rpc_socks_match_replies",
     "xdrg_rpc_socks_call_stats", "xdrg_rpc_socks_pending_retire", "xdrg_rpc_socks_pending_retire_workspace_size",
+    "xdrg_rpc_send_batch", "xdrg_rpc_send_batch_workspace_size",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -231,6 +232,28 @@ class XdrgRpcConn(C.Structure):
 CONN_IN_DTYPE = np.dtype([("begin", "<u8"), ("len", "<u8")])
 CONN_DTYPE = np.dtype([("first", "<u8"), ("consumed", "<u8"), ("msgs", "<u8"), ("need", "<u4"), ("state", "<u4")])
 assert C.sizeof(XdrgRpcConnIn) == CONN_IN_DTYPE.itemsize == 16 and C.sizeof(XdrgRpcConn) == CONN_DTYPE.itemsize == 32
+
+# the send batch (include/xdrgpu.h "The send side")
+RPC_MAX_SEND_SRCS = 64       # XDRG_RPC_MAX_SEND_SRCS
+RPC_SEND_SORT_TILE = 2048    # XDRG_RPC_SEND_SORT_TILE: entries a workgroup of a sort pass
+SEND_DROPPED, SEND_EMPTY, SEND_UNUSABLE = -1, -2, -3  # d_pos of an entry that is not queued
+
+
+class XdrgRpcSendSrc(C.Structure):
+    """xdrg_rpc_send_src: one message stream for xdrg_rpc_send_batch (a HOST
+    record of device pointers)."""
+    _fields_ = [("d_bytes", C.c_void_p), ("d_offsets", C.c_void_p), ("d_conn", C.c_void_p),
+                ("d_count", C.c_void_p), ("bytes_len", C.c_uint64), ("count_cap", C.c_uint32),
+                ("conn", C.c_uint32)]
+
+
+class XdrgRpcWqueue(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("msgs", C.c_uint64), ("begin", C.c_uint64), ("len", C.c_uint64)]
+
+
+SEND_SRC = XdrgRpcSendSrc
+WQUEUE_DTYPE = np.dtype([("first", "<u8"), ("msgs", "<u8"), ("begin", "<u8"), ("len", "<u8")])
+assert C.sizeof(XdrgRpcSendSrc) == 48 and C.sizeof(XdrgRpcWqueue) == WQUEUE_DTYPE.itemsize == 32
 
 
 _lib = None
@@ -352,6 +375,11 @@ def lib() -> C.CDLL:
     L.xdrg_rpc_socks_pending_retire_workspace_size.restype = sz
     L.xdrg_rpc_socks_pending_retire.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]
     L.xdrg_rpc_socks_pending_retire.restype = C.c_int
+    L.xdrg_rpc_send_batch_workspace_size.argtypes = [u64, u64]
+    L.xdrg_rpc_send_batch_workspace_size.restype = sz
+    L.xdrg_rpc_send_batch.argtypes = [C.POINTER(XdrgRpcSendSrc), u32, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, sz, vp, vp]
+    L.xdrg_rpc_send_batch.restype = C.c_int
     L.xdrg_record_depths.argtypes = [vp, vp, u64, vp, u64, vp, vp, sz, vp, vp]
     L.xdrg_record_depths.restype = C.c_int
     L.xdrg_serial_sizes.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, sz, vp, vp]

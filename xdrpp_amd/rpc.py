@@ -39,13 +39,18 @@ Host-side mirror of the reference's RPC message handling, batched:
       a framing error closing its own connection only; and
       rpc_sock::recv_msg's test (msgsock.cc:202-225)        -> Receiver, recv_batch(),
                                                                Received.reply_ranges()
+    msg_sock::putmsg for many sockets at once (msgsock.cc:
+      121-134): message streams in any order routed to their
+      connections' write queues; pop_wbytes and output
+      (msgsock.cc:137-188) on the host                      -> send_batch(), Sender,
+                                                               socks_call_batch_any_order()
 
 Each header decodes to one 64-byte xdrg_rpc_hdr (HDR_DTYPE below).  The
 exceptions a client raises for a reply (xdr_call_error with the
 rpc_call_stat message, exception.h:25-57, rpc_msg.cc:8-109) come from
 raise_for_reply().  Every byte is produced by the HIP kernels of
 libxdrgpu.so (xdrpp_amd/csrc/rpc.hip, verify.hip, replies.hip,
-reply_batch.hip, call_batch.hip, settle.hip, recv_batch.hip).
+reply_batch.hip, call_batch.hip, settle.hip, recv_batch.hip, send_batch.hip).
 """
 from __future__ import annotations
 
@@ -1417,3 +1422,259 @@ def socks_settle(received, pending: SockCalls, plans: dict[int, Plan | None], cl
     old_of_new = slot[:k]
     pending2 = SockCalls.from_device(kept[:k], kept_sock[:k], pos[old_of_new], pending.last)
     return stats[pending.inv], results, pending2, old_of_new
+
+
+def socks_call_batch_any_order(pending: SockCalls, socks, sources: list, capacity: int | None = None):
+    """socks_call_batch() for calls in application order: socks[i] is call i's
+    socket, in any order.  The calls are brought into socket order by a stable
+    sort (calls to one socket keep their order, so each rpc_sock hands out its
+    xids in the order the application called), every ArgSource.index is
+    renumbered, and socks_call_batch does the rest.  Returns (stream, offsets,
+    xids, pending2, ranges, order): stream, offsets and ranges as
+    socks_call_batch returns them, in socket order, message p of the stream
+    being call order[p] (int64 [n]); xids int32 [n] and the caller positions
+    of pending2 (call i is ncalls + i) in the application's order.  A socket
+    number outside 0..nsocks-1 raises ValueError.  (A client with ONE xid
+    space over many connections needs none of this: call_batch() in caller
+    order, then send_batch() with the stream, its offsets and conn = socks.)"""
+    import dataclasses
+    srcs = [r if isinstance(r, ArgSource) else arg_source(*r) for r in sources]
+    dev = pending.device
+    n = len(socks) if not isinstance(socks, torch.Tensor) else socks.numel()
+    call_sock = _sock_tensor(socks, n, dev)
+    order = torch.sort(call_sock, stable=True).indices
+    inv = torch.empty_like(order)
+    inv[order] = torch.arange(n, dtype=torch.int64, device=dev)
+
+    def renumber(index: torch.Tensor) -> torch.Tensor:
+        ok = (index >= 0) & (index < n)  # an index that names no call stays what it is
+        return torch.where(ok, inv[index.clamp(0, max(n - 1, 0))], index) if n else index
+
+    srcs = [dataclasses.replace(r, index=renumber(r.index.to(dev))) for r in srcs]
+    out, offs, xids, p2, ranges = socks_call_batch(pending, call_sock[order], srcs, capacity)
+    nc = pending.ncalls
+    pending2 = SockCalls.from_device(p2.table, p2.sock, torch.cat([p2.inv[:nc], p2.inv[nc:][inv]]), p2.last)
+    return out, offs, xids[inv], pending2, ranges, order
+
+
+# ----------------------------------------------------------- the send side
+WQUEUE_DTYPE = A.WQUEUE_DTYPE
+SEND_OUTCOME_NAMES = {A.SEND_DROPPED: "DROPPED", A.SEND_EMPTY: "EMPTY", A.SEND_UNUSABLE: "UNUSABLE"}
+
+
+@dataclass
+class SendSource:
+    """One xdrg_rpc_send_src: a stream of record-marked messages (reply_batch's,
+    call_batch's, recv_batch's), offsets int64 [count + 1], and the connection
+    of every entry: conn an int32 [count] device tensor, or an int for a
+    stream that goes to one connection.  count: an int64 [1] device tensor
+    read by the kernels (min(count, count_cap) entries are used), or None."""
+    stream: torch.Tensor
+    offsets: torch.Tensor
+    conn: torch.Tensor | int
+    count: torch.Tensor | None = None
+    count_cap: int | None = None
+
+    @property
+    def cap(self) -> int:
+        return max(self.offsets.numel() - 1, 0) if self.count_cap is None else self.count_cap
+
+
+def send_source(stream: torch.Tensor, offsets: torch.Tensor, conn) -> SendSource:
+    """A SendSource from (stream, offsets, conn): conn an int, or one
+    connection number per entry (a tensor, an array, a list)."""
+    if isinstance(conn, (int, np.integer)):
+        return SendSource(stream, offsets, int(conn))
+    return SendSource(stream, offsets, _sock_tensor(conn, max(offsets.numel() - 1, 0), stream.device))
+
+
+def _send_srcs(sources) -> "C.Array":
+    if len(sources) > A.RPC_MAX_SEND_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_SEND_SRCS} message streams per call")
+    arr = (A.XdrgRpcSendSrc * max(len(sources), 1))()
+    for k, r in enumerate(sources):
+        one = not isinstance(r.conn, torch.Tensor)
+        arr[k] = A.XdrgRpcSendSrc(_ptr(r.stream), _ptr(r.offsets), None if one else _ptr(r.conn), _ptr(r.count),
+                                  r.stream.numel(), r.cap, r.conn if one else 0)
+    return arr
+
+
+def launch_send_batch(sources: list[SendSource], nconns: int, closed: torch.Tensor | None, out: torch.Tensor,
+                      offsets: torch.Tensor, count: torch.Tensor, conn_of: torch.Tensor, origin: torch.Tensor,
+                      pos: torch.Tensor | None, queues: torch.Tensor, counts: torch.Tensor | None, status: Status,
+                      ws: torch.Tensor, stream=None) -> None:
+    """xdrg_rpc_send_batch as it is: closed int32 [nconns] or None, out uint8,
+    offsets int64 [entries + 1] (entries = the sum of the sources' cap), count
+    int64 [1], conn_of int32 [entries], origin int64 [entries], pos int64
+    [entries] or None, queues int64 [4 nconns] (xdrg_rpc_wqueue records),
+    counts int64 [4] or None, ws uint8 of
+    xdrg_rpc_send_batch_workspace_size(entries, nconns) bytes.  `status` is not
+    initialised here.  Kernels only: capturable."""
+    A.check(A.lib().xdrg_rpc_send_batch(_send_srcs(sources), len(sources), nconns, _ptr(closed), _ptr(out),
+                                        out.numel(), offsets.data_ptr(), count.data_ptr(), _ptr(conn_of),
+                                        _ptr(origin), _ptr(pos), _ptr(queues), _ptr(counts), _ptr(ws), ws.numel(),
+                                        status.ptr, _stream() if stream is None else stream),
+            "xdrg_rpc_send_batch")
+
+
+def wqueues_numpy(queues: torch.Tensor) -> np.ndarray:
+    """Device xdrg_rpc_wqueue array -> numpy structured array (copies)."""
+    return queues.cpu().numpy().view(WQUEUE_DTYPE).reshape(-1)
+
+
+@dataclass
+class Queued:
+    """What send_batch() queued: `stream` uint8, every connection's messages
+    contiguous and in putmsg order; `offsets` int64 [count + 1], the mark of
+    queue position j and then the end; `count`; `conn_of` int32 [count];
+    `origin` int64 [count], source << 32 | entry; `pos` int64 [entries], the
+    queue position of every entry in source-major order, or SEND_DROPPED,
+    SEND_EMPTY, SEND_UNUSABLE; `queues` int64 [4 nconns], the 32-byte
+    xdrg_rpc_wqueue records (queues_numpy()); `counts` = (queued, dropped,
+    empty, unusable)."""
+    stream: torch.Tensor
+    offsets: torch.Tensor
+    count: int
+    conn_of: torch.Tensor
+    origin: torch.Tensor
+    pos: torch.Tensor
+    queues: torch.Tensor
+    counts: tuple
+
+    def queues_numpy(self) -> np.ndarray:
+        return wqueues_numpy(self.queues)
+
+    def ranges(self) -> np.ndarray:
+        """int64 [nconns, 2]: connection c's bytes are stream[ranges[c, 0]:
+        ranges[c, 1]], one writev; consecutive ranges tile the stream."""
+        q = self.queues_numpy()
+        b = q["begin"].astype(np.int64)
+        return np.stack([b, b + q["len"].astype(np.int64)], axis=1)
+
+
+def send_batch(sources: list, nconns: int, closed=None, capacity: int | None = None) -> Queued:
+    """msg_sock::putmsg for many message streams and connections at once
+    (xdrg_rpc_send_batch; msgsock.cc:121-134).  sources: a list of (stream,
+    offsets, conn) -- see send_source() -- or SendSource, at most 64:
+    ValueError beyond; putmsg order on a connection is source 0 first, each
+    source in entry order.  closed: one flag per connection (a tensor, an
+    array, Sender.closed()) or None; a closed connection's messages are
+    dropped (wfail_, :124-127).  One sync, for the totals.  capacity: bytes of
+    the output, by default the sum of the streams' bytes, which holds whatever
+    sources with disjoint entries can queue; a smaller one (or overlapping
+    entries) raises XdrRuntimeError (XDRG_ERR_OVERFLOW_PUT) with record = the
+    first queue position that does not fit."""
+    srcs = [r if isinstance(r, SendSource) else send_source(*r) for r in sources]
+    if len(srcs) > A.RPC_MAX_SEND_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_SEND_SRCS} message streams per call")
+    dev = srcs[0].stream.device if srcs else torch.device("cuda")
+    entries = sum(r.cap for r in srcs)
+    L = A.lib()
+    cap = sum(r.stream.numel() for r in srcs) if capacity is None else capacity
+    if closed is not None:
+        closed = _sock_tensor(closed, nconns, dev)
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
+    offs = torch.empty(entries + 1, dtype=torch.int64, device=dev)
+    cnt = torch.empty(1, dtype=torch.int64, device=dev)
+    conn_of = torch.empty(max(entries, 1), dtype=torch.int32, device=dev)[:entries]
+    origin = torch.empty(max(entries, 1), dtype=torch.int64, device=dev)[:entries]
+    pos = torch.empty(max(entries, 1), dtype=torch.int64, device=dev)[:entries]
+    queues = torch.empty(max(4 * nconns, 4), dtype=torch.int64, device=dev)[:4 * nconns]
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(L.xdrg_rpc_send_batch_workspace_size(entries, nconns), 16), dtype=torch.uint8, device=dev)
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    launch_send_batch(srcs, nconns, closed, out, offs, cnt, conn_of, origin, pos, queues, counts, st, ws, s)
+    e = st.read(s)
+    if e.code:
+        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    n = int(cnt.item())
+    return Queued(out[:int(e.total_bytes)], offs[:n + 1], n, conn_of[:n], origin[:n], pos, queues,
+                  tuple(int(v) for v in counts.tolist()))
+
+
+class Sender:
+    """The host's wqueue_ / wstart_ / wsize_ / wfail_ (msgsock.h) for many
+    connections: the messages each has queued and not yet written.  Host code
+    only, the mirror of Receiver; the queueing order is send_batch's.
+
+        tx.queue(send_batch(sources, nconns, tx.closed(nconns)))
+        n = os.writev(fd, tx.iov(conn))     # msg_sock::output, msgsock.cc:157-188
+        tx.wrote(conn, n)                   # or tx.fail(conn); EAGAIN: nothing
+    """
+
+    def __init__(self):
+        self._queue: dict = {}   # connection -> list of memoryviews, the front one whole (wqueue_)
+        self._start: dict = {}   # connection -> bytes of the front message already written (wstart_)
+        self._size: dict = {}    # connection -> bytes queued and not written (wsize_)
+        self.failed: set = set()  # connections with wfail_
+
+    def putmsg(self, conn, msg) -> None:
+        """msg_sock::putmsg (msgsock.cc:121-134) without the output() it
+        starts: dropped after a failure, else queued whole."""
+        if conn in self.failed:
+            return
+        m = memoryview(msg).cast("B")
+        self._size[conn] = self._size.get(conn, 0) + len(m)
+        self._queue.setdefault(conn, []).append(m)
+
+    def queue(self, queued: Queued, ids=None) -> None:
+        """Take every connection's range of a Queued (one download of the
+        stream): putmsg for each of its messages in queue order.  ids[c] names
+        connection c of the batch (default: c itself)."""
+        data = queued.stream.cpu().numpy()
+        offs = queued.offsets.cpu().numpy()
+        for c, q in enumerate(queued.queues_numpy()):
+            first, msgs = int(q["first"]), int(q["msgs"])
+            conn = c if ids is None else ids[c]
+            for j in range(first, first + msgs):
+                self.putmsg(conn, data[int(offs[j]):int(offs[j + 1])].data)
+
+    def pending(self, conn) -> int:
+        """wsize_: bytes queued for conn and not yet written."""
+        return self._size.get(conn, 0)
+
+    def iov(self, conn, maxiov: int = 8) -> list:
+        """What output() hands writev (msgsock.cc:160-172): at most maxiov
+        buffers, the first from wstart_."""
+        q = self._queue.get(conn, [])
+        return [m[self._start.get(conn, 0):] if i == 0 else m for i, m in enumerate(q[:maxiov])]
+
+    def wrote(self, conn, n: int) -> None:
+        """pop_wbytes(n) (msgsock.cc:137-155) after a writev that returned n
+        > 0 (0 is a no-op, as there)."""
+        if n == 0:
+            return
+        if n < 0 or n > self.pending(conn):
+            raise ValueError(f"wrote({conn!r}, {n}): {self.pending(conn)} bytes are queued")
+        self._size[conn] -= n
+        q = self._queue[conn]
+        front = len(q[0]) - self._start.get(conn, 0)
+        if n < front:
+            self._start[conn] = self._start.get(conn, 0) + n
+            return
+        n -= front
+        done = 1
+        while n > 0 and n >= len(q[done]):
+            n -= len(q[done])
+            done += 1
+        del q[:done]
+        self._start[conn] = n
+
+    def fail(self, conn) -> None:
+        """writev failed with anything but EAGAIN (msgsock.cc:175-179): the
+        queue is cleared, and whatever is queued later is dropped."""
+        self.failed.add(conn)
+        self._queue.pop(conn, None)
+        self._start.pop(conn, None)
+        self._size.pop(conn, None)
+
+    def closed(self, nconns: int, ids=None) -> torch.Tensor:
+        """The d_closed array of the next send_batch: int32 [nconns] (on the
+        host), 1 where connection ids[c] (default: c) has failed."""
+        t = torch.zeros(nconns, dtype=torch.int32)
+        for c in range(nconns):
+            if (c if ids is None else ids[c]) in self.failed:
+                t[c] = 1
+        return t
