@@ -29,6 +29,7 @@ import call_stream_model as CS  # noqa: E402
 import oracle_bridge as O  # noqa: E402
 import reply_model as RM  # noqa: E402
 import settle_model as SM  # noqa: E402
+import socks_model as KM  # noqa: E402
 
 SUCCESS = (A.RPCS_ACCEPT_STAT, 0)
 
@@ -349,6 +350,53 @@ def test_abort(dev, loop, round1):
     assert p3.ncalls == 0 and old3.numel() == 0 and p3.last_xid == p2.last_xid
     plain = R.call_stats_numpy(loop.settle(s, o, p2)[0])
     assert np.array_equal(plain[::4], got[::4]) and (np.delete(plain, np.s_[::4])["type"] == A.RPCS_PENDING).all()
+
+
+# ----------------------------------------------------------------- edges
+@pytest.mark.parametrize("aborted", [False, True])
+@pytest.mark.parametrize("nmsgs", [0, 2])
+def test_settle_on_an_empty_table(dev, nmsgs, aborted):
+    """settle(), decode_results() and retire() with no pending call: every
+    well-formed reply is a reply to an unknown call, and everything per call
+    comes back empty with last_xid kept."""
+    s, o = KM.reply_stream([5, 0xFFFFFFFE][:nmsgs])
+    none = np.zeros(0, np.uint32)
+    plans, cps = {0: None, 1: M.Plan(S.rec128)}, {0: None, 1: compile_plan(S.rec128)}
+    want_h, want_call, want_reply, want_stats, (want_table, want_old, want_inv) = SM.settle(s, o, none, none, cps,
+                                                                                          aborted=aborted)
+    assert len(want_h) == nmsgs and (want_h["action"] == A.RPCR_UNKNOWN_XID).all() and (want_call == -1).all()
+    assert len(want_reply) == len(want_stats) == len(want_table) == len(want_old) == len(want_inv) == 0
+    p = R.PendingCalls(none, none, dev, last_xid=0xFFFFFFF7)
+    empty = R.PendingCalls(none, none, dev, last_xid=0xFFFFFFF7)
+    st, od = to_dev(s, dev), u64_dev(o, dev)
+    stats, results, p2, old_of_new = R.settle(st, od, p, plans, aborted=aborted)
+    assert stats.numel() == 0 and stats.dtype == torch.int64 and len(R.call_stats_numpy(stats)) == 0
+    same_pending(p2, empty)
+    assert old_of_new.numel() == 0 and old_of_new.dtype == torch.int64
+    assert sorted(results) == [0, 1] and all(v[0].numel() == 0 and v[0].dtype == torch.int64 for v in results.values())
+    assert results[0][1:] == (None, None)
+    assert results[1][1].numel() == 0 and results[1][1].dtype == torch.uint8 and results[1][2] is None
+    hd, call, reply_of, out = R.decode_results(st, od, p, plans)
+    assert R.hdrs_numpy(hd).tobytes() == want_h.tobytes() and np.array_equal(call.cpu().numpy(), want_call)
+    assert call.dtype == torch.int64 and reply_of.numel() == 0 and reply_of.dtype == torch.int64
+    assert all(v[0].numel() == 0 for v in out.values())
+    assert R.call_stats(hd, reply_of, p, aborted).numel() == 0
+    q, old = p.retire(reply_of)
+    same_pending(q, empty)
+    assert old.numel() == 0 and old.dtype == torch.int64
+
+
+def test_call_batch_of_no_calls(dev):
+    """n = 0 and no sources on a table of 2 calls: an empty stream, and the
+    table as it was."""
+    p = R.PendingCalls([0xFFFFFFFE, 7], [1, 0], dev, last_xid=0xFFFFFFFE)
+    assert CS.next_xids(p.calls["xid"], p.last_xid, 0).size == 0
+    stream, offs, xids, p2 = R.call_batch(p, [])
+    assert stream.numel() == 0 and stream.dtype == torch.uint8 and offs.cpu().tolist() == [0]
+    assert xids.numel() == 0 and xids.dtype == torch.int32
+    same_pending(p2, p)
+    assert p2.calls.tolist() == [(7, 0), (0xFFFFFFFE, 1)] and p2.inv.cpu().tolist() == [1, 0]
+    same_pending(R.call_batch(p, [], 0)[3], p)
 
 
 # ---------------------------------------------------------- graph capture

@@ -541,6 +541,71 @@ def test_rounds(dev, rounds):
     assert np.array_equal(p3.calls, want_table3) and np.array_equal(p3.socks_numpy(), want_sock3)
 
 
+# ----------------------------------------------------------------- edges
+def settled(dev, socks, xids, res, last, s, o, rows, closed, plans, cps):
+    """socks_settle() on a small table against socks_model; returns (stats as
+    numpy, results, pending2, old_of_new)."""
+    nsocks = len(last)
+    p = R.SockCalls(socks, xids, res, nsocks, dev, last=last)
+    mh, mcall, mreply = KM.match(s, o, KM.msg_socks(rows, None, nsocks), socks, xids)
+    RM.verify_results(s, mh, mcall, np.broadcast_to(np.asarray(res, dtype=np.int64), (len(xids),)), cps)
+    mstats = KM.call_stats(mh, mreply, socks, closed)
+    msock2, mtable2, mold, minv = KM.retire(socks, xids, res, mreply, closed)
+    hd, call, reply_of = R.socks_match_replies(to_dev(s, dev), u64_dev(o, dev), i32_dev(rows, dev), p)
+    assert R.hdrs_numpy(hd).tobytes() == mh.tobytes()  # no reply here has a result to verify
+    assert np.array_equal(call.cpu().numpy(), mcall) and np.array_equal(reply_of.cpu().numpy(), mreply)
+    assert call.dtype == reply_of.dtype == torch.int64
+    stats, results, p2, old_of_new = R.socks_settle((to_dev(s, dev), u64_dev(o, dev), i32_dev(rows, dev)), p, plans,
+                                                    i32_dev(closed, dev))
+    assert stats.dtype == torch.int64 and np.array_equal(R.call_stats_numpy(stats), mstats)
+    assert old_of_new.dtype == torch.int64 and np.array_equal(old_of_new.cpu().numpy(), mold)
+    assert p2.ncalls == len(mtable2) and np.array_equal(p2.calls, mtable2) and np.array_equal(p2.socks_numpy(), msock2)
+    assert np.array_equal(p2.inv.cpu().numpy(), minv) and np.array_equal(p2.perm.cpu().numpy(), np.argsort(minv))
+    assert p2.nsocks == nsocks and torch.equal(p2.last, p.last) and p2.last_numpy().tolist() == list(last)
+    assert p2.table.dtype == torch.int64 and p2.sock.dtype == torch.int32
+    return mh, R.call_stats_numpy(stats), results, p2, old_of_new
+
+
+@pytest.mark.parametrize("closed", [(0, 0, 0), (0, 1, 0)])
+@pytest.mark.parametrize("nmsgs", [0, 2])
+def test_settle_on_an_empty_table(dev, nmsgs, closed):
+    s, o = KM.reply_stream([5, 0xFFFFFFFE][:nmsgs])
+    plans, cps = {0: None, 1: M.Plan(S.rec128)}, {0: None, 1: compile_plan(S.rec128)}
+    mh, st, results, p2, old_of_new = settled(dev, [], [], [], [7, 0, 0xFFFFFFF0], s, o, np.array([0, 2][:nmsgs]),
+                                              np.array(closed), plans, cps)
+    assert len(mh) == nmsgs and (mh["action"] == A.RPCR_UNKNOWN_XID).all()
+    assert len(st) == 0 and p2.ncalls == 0 and old_of_new.numel() == 0
+    assert sorted(results) == [0, 1] and all(v[0].numel() == 0 and v[0].dtype == torch.int64 for v in results.values())
+    assert results[0][1:] == (None, None)
+    assert results[1][1].numel() == 0 and results[1][1].dtype == torch.uint8 and results[1][2] is None
+
+
+def test_settle_that_leaves_no_call(dev):
+    """3 calls over 2 sockets, each answered or on the closed socket: count is
+    0, and the stats come in the caller's order."""
+    socks, xids = np.array([1, 0, 1]), np.array([5, 5, 9])
+    s, o = KM.reply_stream([9, 5])
+    _, st, results, p2, old_of_new = settled(dev, socks, xids, 0, [5, 9], s, o, np.array([1, 0]), np.array([0, 1]),
+                                             {0: None}, {0: None})
+    assert st.tolist() == [(A.RPCS_NETWORK_ERROR, 0), SUCCESS, SUCCESS]
+    assert p2.ncalls == 0 and old_of_new.numel() == 0
+    assert results[0][0].cpu().tolist() == [0, 1] and results[0][1:] == (None, None)
+
+
+def test_call_batch_of_no_calls(dev):
+    """n = 0 and no sources on a table of 2 calls: an empty stream, and the
+    table as it was."""
+    p = R.SockCalls([2, 0], [7, 7], [1, 0], 3, dev, last=[7, 0, 0xFFFFFFFE])
+    stream, offs, xids, p2, ranges = R.socks_call_batch(p, [], [])
+    assert stream.numel() == 0 and stream.dtype == torch.uint8 and offs.cpu().tolist() == [0]
+    assert xids.numel() == 0 and xids.dtype == torch.int32
+    assert ranges.tolist() == [[0, 0]] * 3 and ranges.dtype == np.int64
+    assert p2.ncalls == 2 and p2.nsocks == 3 and np.array_equal(p2.calls, p.calls)
+    for a in ("table", "sock", "inv", "perm", "last"):
+        assert torch.equal(getattr(p2, a), getattr(p, a)), a
+    assert p2.calls.tolist() == [(7, 0), (7, 1)] and p2.socks_numpy().tolist() == [0, 2]
+
+
 # ---------------------------------------------------------- graph capture
 def test_graph_capture(dev):
     """One capture of launch_socks_match_replies -> launch_verify_results ->

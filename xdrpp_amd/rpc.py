@@ -126,6 +126,26 @@ def raise_for_reply(h, record: int | None = None) -> None:
     raise _EXC.get(A.lib().xdrg_error_exception(code), XdrRuntimeError)(what, record, None, code)
 
 
+# ----------------------------------------------------------------- status
+def _raise_status(e: A.XdrgError) -> None:
+    """The XdrRuntimeError of a status block that holds an error (a batch
+    stage's own: an output that is too small); returns for none."""
+    if e.code:
+        raise XdrRuntimeError(A.lib().xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+
+
+def _run_status(dev, launch) -> A.XdrgError:
+    """launch(status, stream) on the current stream with a fresh Status, then
+    the one read of it: raises what it holds, else returns it (total_bytes)."""
+    st = Status(dev)
+    s = _stream()
+    st.init(s)
+    launch(st, s)
+    e = st.read(s)
+    _raise_status(e)
+    return e
+
+
 # --------------------------------------------------------------- registry
 def proc_table(services: dict[int, dict[int, list[int]]]) -> np.ndarray:
     """The sorted (prog, vers, proc, flags) table xdrg_rpc_dispatch takes,
@@ -213,9 +233,7 @@ class ReplyWriter:
         self.status.init(s)
         self.launch(hdrs, out, offs, s)
         e = self.status.read(s)
-        if e.code:
-            raise XdrRuntimeError(A.lib().xdrg_error_message(e.code).decode(), int(e.record),
-                                  None, int(e.code))
+        _raise_status(e)
         return out[:int(e.total_bytes)], offs
 
 
@@ -265,6 +283,26 @@ def verify_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tupl
     return verdicts[:n]
 
 
+def _gather(stream_bytes, hdrs, capacity, ws_size, call):
+    """What gather_args and gather_results share.  ws_size(n): the C call's
+    workspace size; call(n, *tail) makes the C call, `tail` being the arguments
+    both end with: out, capacity, offsets, index, count, workspace and its
+    size, status, stream."""
+    dev = hdrs.device
+    n = hdrs.numel() // A.RPC_HDR_BYTES
+    # (the pieces gathered are disjoint pieces of the stream: its length holds them)
+    cap = stream_bytes.numel() if capacity is None else capacity
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    index = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(ws_size(n), 16), dtype=torch.uint8, device=dev)
+    e = _run_status(dev, lambda st, s: call(n, out.data_ptr(), cap, offs.data_ptr(), index.data_ptr(), cnt.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), st.ptr, s))
+    count = int(cnt.item())
+    return out[:int(e.total_bytes)], offs[:count + 1], index[:count]
+
+
 def gather_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, key: tuple[int, int, int],
                 capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The arguments of procedure key = (prog, vers, proc)'s dispatched calls
@@ -275,28 +313,28 @@ def gather_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, key: tuple[int, 
     (default: the stream's length, which always holds them); a smaller one
     raises XdrRuntimeError (XDRG_ERR_OVERFLOW_PUT) with record = the first
     message that does not fit."""
-    dev = hdrs.device
-    n = hdrs.numel() // A.RPC_HDR_BYTES
     L = A.lib()
-    # (the arguments are disjoint pieces of the stream: its length holds them)
-    cap = stream_bytes.numel() if capacity is None else capacity
-    args = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)
-    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    index = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.xdrg_rpc_gather_workspace_size(n), 16), dtype=torch.uint8, device=dev)
-    st = Status(dev)
-    s = _stream()
-    st.init(s)
     prog, vers, proc = key
-    A.check(L.xdrg_rpc_gather_args(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), n, prog, vers, proc,
-                                   args.data_ptr(), cap, offs.data_ptr(), index.data_ptr(), cnt.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), st.ptr, s), "xdrg_rpc_gather_args")
-    e = st.read(s)
-    if e.code:
-        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
-    count = int(cnt.item())
-    return args[:int(e.total_bytes)], offs[:count + 1], index[:count]
+    return _gather(stream_bytes, hdrs, capacity, L.xdrg_rpc_gather_workspace_size, lambda n, *tail: A.check(
+        L.xdrg_rpc_gather_args(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), n, prog, vers, proc, *tail),
+        "xdrg_rpc_gather_args"))
+
+
+def _decode_each(plans: dict, gather, dev, stack_limit: int) -> dict:
+    """{key: (index, native, heap)} for every key of `plans`, in order:
+    gather(key) gives (bytes, offsets, index), and Marshaler.decode the
+    records.  A void plan (None) has native = heap = None."""
+    out = {}
+    for key in sorted(plans):
+        data, offs, index = gather(key)
+        if plans[key] is None:
+            out[key] = (index, None, None)
+        elif index.numel() == 0:  # no entry of this key is left
+            out[key] = (index, torch.empty(0, dtype=torch.uint8, device=dev), None)
+        else:
+            native, heap = Marshaler(plans[key], dev).decode(data, index.numel(), offs, stack_limit)
+            out[key] = (index, native, heap)
+    return out
 
 
 def decode_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tuple[int, int, int], Plan],
@@ -309,15 +347,7 @@ def decode_args(stream_bytes: torch.Tensor, hdrs: torch.Tensor, plans: dict[tupl
     keys = sorted(plans)
     for k0 in range(0, len(keys), A.RPC_MAX_ARGPLANS):
         verify_args(stream_bytes, hdrs, {k: plans[k] for k in keys[k0:k0 + A.RPC_MAX_ARGPLANS]}, stack_limit)
-    out = {}
-    for key in keys:
-        args, offs, index = gather_args(stream_bytes, hdrs, key)
-        if index.numel() == 0:  # no call of this procedure is left
-            out[key] = (index, torch.empty(0, dtype=torch.uint8, device=hdrs.device), None)
-            continue
-        native, heap = Marshaler(plans[key], hdrs.device).decode(args, index.numel(), offs, stack_limit)
-        out[key] = (index, native, heap)
-    return out
+    return _decode_each(plans, lambda key: gather_args(stream_bytes, hdrs, key), hdrs.device, stack_limit)
 
 
 # ------------------------------------------------------ the reply stream
@@ -427,20 +457,13 @@ def reply_batch(hdrs: torch.Tensor, results: list, capacity: int | None = None) 
         raise ValueError(f"at most {A.RPC_MAX_RESULT_SRCS} result sources per call")
     dev = hdrs.device
     n = hdrs.numel() // A.RPC_HDR_BYTES
-    L = A.lib()
     cap = capacity
     if cap is None:
         cap = 36 * n + sum(28 * r.cap + (0 if r.xdr is None else r.xdr.numel()) for r in srcs)
     out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
     offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.xdrg_rpc_reply_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
-    st = Status(dev)
-    s = _stream()
-    st.init(s)
-    launch_reply_batch(hdrs, srcs, out, offs, None, st, ws, s)
-    e = st.read(s)
-    if e.code:
-        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    ws = torch.empty(max(A.lib().xdrg_rpc_reply_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
+    e = _run_status(dev, lambda st, s: launch_reply_batch(hdrs, srcs, out, offs, None, st, ws, s))
     return out[:int(e.total_bytes)], offs
 
 
@@ -507,6 +530,39 @@ class _CallTable:
             return call
         return torch.where(call >= 0, self.inv[call.clamp(min=0)], call)
 
+    def calls_to_caller(self, t: torch.Tensor) -> torch.Tensor:
+        """A tensor with one entry per call (reply_of, stats) from table order
+        into the caller's."""
+        return t[self.inv] if self.ncalls else t
+
+    def calls_to_table(self, t: torch.Tensor) -> torch.Tensor:
+        if self.ncalls == 0:
+            return t
+        out = torch.empty_like(t)
+        out[self.inv] = t
+        return out
+
+    def _survivors(self, kept_pos: torch.Tensor, count: torch.Tensor) -> tuple[int, torch.Tensor, torch.Tensor]:
+        """The caller's numbering after a retire launch (its d_kept_pos int64
+        [ncalls] in TABLE positions and d_count): (k, inv2, old_of_new), the
+        survivors renumbered 0..k-1 in ascending old caller position, inv2
+        int64 [k] the new table position of new call p, old_of_new int64 [k]
+        its old caller position.  One sync, for the count; none for an empty
+        table."""
+        dev, nc = self.device, self.ncalls
+        if nc == 0:
+            e = torch.empty(0, dtype=torch.int64, device=dev)
+            return 0, e, e.clone()
+        pos = kept_pos[self.inv]  # a survivor's new table position, by old caller position
+        alive = pos >= 0
+        rank = torch.cumsum(alive, 0) - 1
+        k = int(count.item())  # the one sync
+        # survivor c is new call rank[c]; the retired ones all land on a spare slot k
+        slot = torch.empty(k + 1, dtype=torch.int64, device=dev)
+        slot.scatter_(0, torch.where(alive, rank, k), torch.arange(nc, dtype=torch.int64, device=dev))
+        old_of_new = slot[:k]
+        return k, pos[old_of_new], old_of_new
+
 
 def _as_u32(v, shape=None) -> np.ndarray:
     """Integers of the host or the device as uint32 (mod 2^32), flat or broadcast to `shape`."""
@@ -557,25 +613,15 @@ class PendingCalls(_CallTable):
         without a host sort or a host copy of the table.  One sync, for the
         count."""
         dev, nc = self.device, self.ncalls
-        if nc == 0:
-            e = torch.empty(0, dtype=torch.int64, device=dev)
-            return PendingCalls.from_device(e, e.clone(), last_xid=self.last_xid), e.clone()
-        treply = torch.empty_like(reply_of)
-        treply[self.inv] = reply_of
         kept = torch.empty(nc, dtype=torch.int64, device=dev)
         kept_pos = torch.empty(nc, dtype=torch.int64, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)
-        ws = torch.empty(max(A.lib().xdrg_rpc_pending_retire_workspace_size(nc), 16), dtype=torch.uint8, device=dev)
-        launch_pending_retire(self, treply, kept, kept_pos, count, ws)
-        pos = kept_pos[self.inv]  # a survivor's new table position, by old caller position
-        alive = pos >= 0
-        rank = torch.cumsum(alive, 0) - 1
-        k = int(count.item())  # the one sync
-        # survivor c is call rank[c] of pending2; the retired ones all land on a spare slot k
-        slot = torch.empty(k + 1, dtype=torch.int64, device=dev)
-        slot.scatter_(0, torch.where(alive, rank, k), torch.arange(nc, dtype=torch.int64, device=dev))
-        old_of_new = slot[:k]
-        return PendingCalls.from_device(kept[:k], pos[old_of_new], last_xid=self.last_xid), old_of_new
+        if nc:  # an empty table: nothing is launched and nothing read
+            ws = torch.empty(max(A.lib().xdrg_rpc_pending_retire_workspace_size(nc), 16), dtype=torch.uint8,
+                             device=dev)
+            launch_pending_retire(self, self.calls_to_table(reply_of), kept, kept_pos, count, ws)
+        k, inv2, old_of_new = self._survivors(kept_pos, count)
+        return PendingCalls.from_device(kept[:k], inv2, last_xid=self.last_xid), old_of_new
 
 
 # ------------------------------------------------ the client's call stream
@@ -645,6 +691,47 @@ def launch_pending_add(pending: PendingCalls, new: torch.Tensor, merged: torch.T
             "xdrg_rpc_pending_add")
 
 
+def _as_arg_sources(sources: list) -> list[ArgSource]:
+    srcs = [r if isinstance(r, ArgSource) else arg_source(*r) for r in sources]
+    if len(srcs) > A.RPC_MAX_ARG_SRCS:
+        raise ValueError(f"at most {A.RPC_MAX_ARG_SRCS} argument sources per call")
+    return srcs
+
+
+def _call_batch(pending: _CallTable, srcs: list[ArgSource], n: int, capacity: int | None, next_xids, pending_add):
+    """What call_batch and socks_call_batch share: next_xids(xids, stream),
+    launch_call_batch and pending_add(sent, merged, old_pos, new_pos, stream)
+    on one stream, then the one sync.  The two callables launch the table's
+    own xid and merge kernels.  Returns (stream, offsets, xids, merged, inv):
+    the new table and the table position of every caller's call, old calls
+    first."""
+    dev, nc = pending.device, pending.ncalls
+    cap = capacity
+    if cap is None:
+        cap = 44 * n + sum(0 if r.xdr is None else r.xdr.numel() for r in srcs)
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
+    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    xids = torch.empty(n, dtype=torch.int32, device=dev)
+    sent = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    merged = torch.empty(nc + n, dtype=torch.int64, device=dev)
+    pos = torch.empty(nc + n, dtype=torch.int64, device=dev)
+    old_pos, new_pos = pos[:nc], pos[nc:]
+    ws = torch.empty(max(A.lib().xdrg_rpc_call_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
+
+    def launch(st, s):
+        next_xids(xids, s)
+        launch_call_batch(xids, srcs, out, offs, sent, counts, st, ws, s)
+        pending_add(sent, merged, old_pos, new_pos, s)
+        unsent, unused = counts.tolist()  # the one sync; the status read that follows is ready
+        if unsent or unused:
+            raise ValueError(f"call_batch: {unsent} call positions without a usable entry, {unused} entries unused")
+
+    e = _run_status(dev, launch)
+    # the caller's call c sits where its old table position went; call i where new entry i went
+    return out[:int(e.total_bytes)], offs, xids, merged, torch.cat([old_pos[pending.inv], new_pos])
+
+
 def call_batch(pending: PendingCalls, sources: list, n: int | None = None,
                capacity: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, PendingCalls]:
     """asynchronous_client_base::invoke (arpc.h:41-59) for a batch of n calls
@@ -666,42 +753,14 @@ def call_batch(pending: PendingCalls, sources: list, n: int | None = None,
     + the argument bytes, which always holds them); a smaller one raises
     XdrRuntimeError (XDRG_ERR_OVERFLOW_PUT) with record = the first call that
     does not fit."""
-    srcs = [r if isinstance(r, ArgSource) else arg_source(*r) for r in sources]
-    if len(srcs) > A.RPC_MAX_ARG_SRCS:
-        raise ValueError(f"at most {A.RPC_MAX_ARG_SRCS} argument sources per call")
-    dev = pending.device
+    srcs = _as_arg_sources(sources)
     if n is None:
         n = sum(r.cap for r in srcs)
-    L = A.lib()
-    cap = capacity
-    if cap is None:
-        cap = 44 * n + sum(0 if r.xdr is None else r.xdr.numel() for r in srcs)
-    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
-    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    xids = torch.empty(n, dtype=torch.int32, device=dev)
-    sent = torch.empty(n, dtype=torch.int64, device=dev)
-    counts = torch.empty(2, dtype=torch.int64, device=dev)
-    merged = torch.empty(pending.ncalls + n, dtype=torch.int64, device=dev)
-    pos = torch.empty(pending.ncalls + n, dtype=torch.int64, device=dev)  # old_pos, then new_pos
-    ws = torch.empty(max(L.xdrg_rpc_call_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
-    st = Status(dev)
-    s = _stream()
-    st.init(s)
-    launch_next_xids(pending, xids, s)
-    launch_call_batch(xids, srcs, out, offs, sent, counts, st, ws, s)
-    launch_pending_add(pending, sent, merged, pos[:pending.ncalls], pos[pending.ncalls:], s)
-    e = st.read(s)  # the one sync; what follows is ready
-    unsent, unused = counts.tolist()
-    if unsent or unused:
-        raise ValueError(f"call_batch: {unsent} call positions without a usable entry, {unused} entries unused")
-    if e.code:
-        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    out, offs, xids, merged, inv = _call_batch(
+        pending, srcs, n, capacity, lambda xids, s: launch_next_xids(pending, xids, s),
+        lambda sent, merged, old_pos, new_pos, s: launch_pending_add(pending, sent, merged, old_pos, new_pos, s))
     last = int(xids[-1].item()) & 0xFFFFFFFF if n else pending.last_xid
-    # the caller's call c sits where its old table position went; call i where new entry i went
-    old_pos, new_pos = pos[:pending.ncalls], pos[pending.ncalls:]
-    inv = torch.cat([old_pos[pending.inv], new_pos])
-    pending2 = PendingCalls.from_device(merged, inv, last_xid=last)
-    return out[:int(e.total_bytes)], offs, xids, pending2
+    return out, offs, xids, PendingCalls.from_device(merged, inv, last_xid=last)
 
 
 def launch_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, pending: PendingCalls,
@@ -716,6 +775,23 @@ def launch_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, pend
             "xdrg_rpc_match_replies")
 
 
+def _match_t(stream_bytes, offsets, pending: _CallTable, launch):
+    """check_replies, then launch(hdrs, call, reply_of), the table's own match
+    launch.  Returns (hdrs, call [n], reply_of [ncalls]) in TABLE positions."""
+    dev = stream_bytes.device
+    n = offsets.numel() - 1
+    hdrs = check_replies(stream_bytes, offsets)
+    tcall = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    treply = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=dev)
+    launch(hdrs, tcall, treply)
+    return hdrs, tcall[:n], treply[:pending.ncalls]
+
+
+def _match_replies_t(stream_bytes, offsets, pending: PendingCalls):
+    return _match_t(stream_bytes, offsets, pending, lambda hdrs, tcall, treply: launch_match_replies(
+        stream_bytes, offsets, pending, hdrs, tcall, treply))
+
+
 def match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor,
                   pending: PendingCalls) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """rpc_sock::recv_msg (msgsock.cc:202-232) for every message: runs
@@ -724,14 +800,8 @@ def match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor,
     call message i answers, reply_of[c] = the message that answers call c, -1
     for none.  The first reply to a call wins; every other reply to it, and
     every reply to no pending call, has action RPCR_UNKNOWN_XID."""
-    dev = stream_bytes.device
-    n = offsets.numel() - 1
-    hdrs = check_replies(stream_bytes, offsets)
-    call = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    reply_of = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=dev)
-    launch_match_replies(stream_bytes, offsets, pending, hdrs, call, reply_of)
-    reply_of = reply_of[:pending.ncalls]
-    return hdrs, pending.to_caller(call[:n]), reply_of[pending.inv] if pending.ncalls else reply_of
+    hdrs, tcall, treply = _match_replies_t(stream_bytes, offsets, pending)
+    return hdrs, pending.to_caller(tcall), pending.calls_to_caller(treply)
 
 
 def _res_runs(plans: dict) -> list[list[int]]:
@@ -783,27 +853,19 @@ def verify_results(stream_bytes: torch.Tensor, hdrs: torch.Tensor, call: torch.T
 
 
 def _gather_results_t(stream_bytes, hdrs, tcall, pending, res, capacity=None):
-    dev = hdrs.device
-    n = hdrs.numel() // A.RPC_HDR_BYTES
     L = A.lib()
-    cap = stream_bytes.numel() if capacity is None else capacity
-    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)
-    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    index = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.xdrg_rpc_gather_results_workspace_size(n), 16), dtype=torch.uint8, device=dev)
-    st = Status(dev)
-    s = _stream()
-    st.init(s)
-    A.check(L.xdrg_rpc_gather_results(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), _ptr(tcall), n,
-                                      _ptr(pending.table), pending.ncalls, res, out.data_ptr(), cap,
-                                      offs.data_ptr(), index.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      st.ptr, s), "xdrg_rpc_gather_results")
-    e = st.read(s)
-    if e.code:
-        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
-    count = int(cnt.item())
-    return out[:int(e.total_bytes)], offs[:count + 1], index[:count]
+    return _gather(stream_bytes, hdrs, capacity, L.xdrg_rpc_gather_results_workspace_size, lambda n, *tail: A.check(
+        L.xdrg_rpc_gather_results(_ptr(stream_bytes), stream_bytes.numel(), _ptr(hdrs), _ptr(tcall), n,
+                                  _ptr(pending.table), pending.ncalls, res, *tail), "xdrg_rpc_gather_results"))
+
+
+def _decode_matched(stream_bytes, hdrs, tcall, pending: _CallTable, plans, stack_limit) -> dict:
+    """The reply step after the match, for either table: verify (the replies
+    that fail become GARBAGE_RES in `hdrs`), then per result type gather and
+    decode.  `tcall` in TABLE positions."""
+    _verify_results_t(stream_bytes, hdrs, tcall, pending, plans, stack_limit)
+    return _decode_each(plans, lambda res: _gather_results_t(stream_bytes, hdrs, tcall, pending, res), hdrs.device,
+                        stack_limit)
 
 
 def gather_results(stream_bytes: torch.Tensor, hdrs: torch.Tensor, call: torch.Tensor, pending: PendingCalls,
@@ -822,25 +884,9 @@ def decode_results(stream_bytes: torch.Tensor, offsets: torch.Tensor, pending: P
     gather_results and Marshaler.decode of the replies left.  Returns (hdrs,
     call, reply_of, {res: (index, native, heap)}); a void result type has
     native = heap = None."""
-    dev = stream_bytes.device
-    n = offsets.numel() - 1
-    hdrs = check_replies(stream_bytes, offsets)
-    tcall = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    reply_of = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=dev)
-    launch_match_replies(stream_bytes, offsets, pending, hdrs, tcall, reply_of)
-    tcall, reply_of = tcall[:n], reply_of[:pending.ncalls]
-    _verify_results_t(stream_bytes, hdrs, tcall, pending, plans, stack_limit)
-    out = {}
-    for res in sorted(plans):
-        data, offs, index = _gather_results_t(stream_bytes, hdrs, tcall, pending, res)
-        if plans[res] is None:
-            out[res] = (index, None, None)
-        elif index.numel() == 0:
-            out[res] = (index, torch.empty(0, dtype=torch.uint8, device=dev), None)
-        else:
-            native, heap = Marshaler(plans[res], dev).decode(data, index.numel(), offs, stack_limit)
-            out[res] = (index, native, heap)
-    return hdrs, pending.to_caller(tcall), reply_of[pending.inv] if pending.ncalls else reply_of, out
+    hdrs, tcall, treply = _match_replies_t(stream_bytes, offsets, pending)
+    out = _decode_matched(stream_bytes, hdrs, tcall, pending, plans, stack_limit)
+    return hdrs, pending.to_caller(tcall), pending.calls_to_caller(treply), out
 
 
 def call_stat_message(h) -> str:
@@ -901,10 +947,9 @@ def call_stats(hdrs: torch.Tensor, reply_of: torch.Tensor, pending: PendingCalls
     stats = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=hdrs.device)[:pending.ncalls]
     if pending.ncalls == 0:
         return stats
-    treply = torch.empty_like(reply_of)
-    treply[pending.inv] = reply_of
-    launch_call_stats(hdrs, treply, stats, A.RPCS_NETWORK_ERROR if aborted else A.RPCS_PENDING)
-    return stats[pending.inv]
+    launch_call_stats(hdrs, pending.calls_to_table(reply_of), stats,
+                      A.RPCS_NETWORK_ERROR if aborted else A.RPCS_PENDING)
+    return pending.calls_to_caller(stats)
 
 
 def call_stats_numpy(stats: torch.Tensor) -> np.ndarray:
@@ -1040,22 +1085,17 @@ def recv_batch(buf: torch.Tensor, segs, max_msg_len: int = A.MSG_SOCK_MAXMSGLEN,
     nconns = segs.numel() // 2
     total = buf.numel()
     max_msgs = total // 4
-    L = A.lib()
     out = torch.empty(max(total, 4), dtype=torch.uint8, device=dev)[:total]
     offs = torch.empty(max_msgs + 1, dtype=torch.int64, device=dev)
     cnt = torch.empty(1, dtype=torch.int64, device=dev)
     conn_of = torch.empty(max(max_msgs, 1), dtype=torch.int32, device=dev)[:max_msgs]
     kind = torch.empty(max(max_msgs, 1), dtype=torch.uint8, device=dev)[:max_msgs] if rpc_sock else None
     conns = torch.empty(max(4 * nconns, 4), dtype=torch.int64, device=dev)[:4 * nconns]
-    ws = torch.empty(max(L.xdrg_rpc_recv_batch_workspace_size(nconns, total), 16), dtype=torch.uint8, device=dev)
-    st = Status(dev)
-    s = _stream()
-    st.init(s)
-    launch_recv_batch(buf, segs, max_msg_len, A.RECV_RPC_SOCK if rpc_sock else 0, out, offs, cnt, conn_of, kind,
-                      conns, st, ws, s)
-    e = st.read(s)
-    if e.code:  # cannot happen with these capacities
-        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    ws = torch.empty(max(A.lib().xdrg_rpc_recv_batch_workspace_size(nconns, total), 16), dtype=torch.uint8,
+                     device=dev)
+    # (no error can come of it with these capacities)
+    e = _run_status(dev, lambda st, s: launch_recv_batch(buf, segs, max_msg_len, A.RECV_RPC_SOCK if rpc_sock else 0,
+                                                         out, offs, cnt, conn_of, kind, conns, st, ws, s))
     n = int(cnt.item())
     return Received(out[:int(e.total_bytes)], offs[:n + 1], n, conn_of[:n], None if kind is None else kind[:n], conns)
 
@@ -1275,51 +1315,26 @@ def socks_call_batch(pending: SockCalls, socks, sources: list, capacity: int | N
     int64 numpy [nsocks, 2], socket g's bytes of the stream (one writev per
     connection; the ranges tile the stream).  In pending2 the old calls keep
     their caller positions and call i is ncalls + i.  Errors as call_batch."""
-    srcs = [r if isinstance(r, ArgSource) else arg_source(*r) for r in sources]
-    if len(srcs) > A.RPC_MAX_ARG_SRCS:
-        raise ValueError(f"at most {A.RPC_MAX_ARG_SRCS} argument sources per call")
+    srcs = _as_arg_sources(sources)
     dev = pending.device
     n = len(socks) if not isinstance(socks, torch.Tensor) else socks.numel()
     call_sock = _sock_tensor(socks, n, dev)
-    L = A.lib()
-    nc = pending.ncalls
-    cap = capacity
-    if cap is None:
-        cap = 44 * n + sum(0 if r.xdr is None else r.xdr.numel() for r in srcs)
-    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=dev)[:cap]
-    offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    xids = torch.empty(n, dtype=torch.int32, device=dev)
-    sent = torch.empty(n, dtype=torch.int64, device=dev)
-    counts = torch.empty(2, dtype=torch.int64, device=dev)
-    merged = torch.empty(nc + n, dtype=torch.int64, device=dev)
-    merged_sock = torch.empty(nc + n, dtype=torch.int32, device=dev)
-    pos = torch.empty(nc + n, dtype=torch.int64, device=dev)  # old_pos, then new_pos
+    merged_sock = torch.empty(pending.ncalls + n, dtype=torch.int32, device=dev)
     last2 = torch.empty_like(pending.last)
-    ws = torch.empty(max(L.xdrg_rpc_call_batch_workspace_size(n), 16), dtype=torch.uint8, device=dev)
     # run ends of every socket in the batch, for the ranges (and the order check)
     ends = torch.searchsorted(call_sock.to(torch.int64),
                               torch.arange(pending.nsocks, dtype=torch.int64, device=dev), right=True)
     ordered = bool((call_sock[1:] >= call_sock[:-1]).all().item()) if n > 1 else True
     if not ordered or (n and (int(call_sock[0].item()) < 0 or int(call_sock[-1].item()) >= pending.nsocks)):
         raise ValueError("socks_call_batch: the calls must be in socket order, sockets 0..nsocks-1")
-    st = Status(dev)
-    s = _stream()
-    st.init(s)
-    launch_socks_next_xids(pending, call_sock, xids, last2, s)
-    launch_call_batch(xids, srcs, out, offs, sent, counts, st, ws, s)
-    launch_socks_pending_add(pending, sent, call_sock, merged, merged_sock, pos[:nc], pos[nc:], s)
-    e = st.read(s)
-    unsent, unused = counts.tolist()
-    if unsent or unused:
-        raise ValueError(f"call_batch: {unsent} call positions without a usable entry, {unused} entries unused")
-    if e.code:
-        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
-    old_pos, new_pos = pos[:nc], pos[nc:]
-    inv = torch.cat([old_pos[pending.inv], new_pos])
+    out, offs, xids, merged, inv = _call_batch(
+        pending, srcs, n, capacity, lambda xids, s: launch_socks_next_xids(pending, call_sock, xids, last2, s),
+        lambda sent, merged, old_pos, new_pos, s: launch_socks_pending_add(pending, sent, call_sock, merged,
+                                                                           merged_sock, old_pos, new_pos, s))
     pending2 = SockCalls.from_device(merged, merged_sock, inv, last2)
     eb = offs[ends].cpu().numpy().astype(np.int64)
     ranges = np.stack([np.concatenate([[0], eb[:-1]]) if eb.size else eb, eb], axis=1).astype(np.int64)
-    return out[:int(e.total_bytes)], offs, xids, pending2, ranges
+    return out, offs, xids, pending2, ranges
 
 
 def _row_sock(ids, dev) -> torch.Tensor | None:
@@ -1330,16 +1345,11 @@ def _row_sock(ids, dev) -> torch.Tensor | None:
 
 
 def _socks_match_t(stream_bytes, offsets, rows, pending, ids):
-    dev = stream_bytes.device
-    n = offsets.numel() - 1
-    hdrs = check_replies(stream_bytes, offsets)
-    tcall = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    reply_of = torch.empty(max(pending.ncalls, 1), dtype=torch.int64, device=dev)
-    row_sock = _row_sock(ids, dev)
+    row_sock = _row_sock(ids, stream_bytes.device)
     nrows = pending.nsocks if row_sock is None else row_sock.numel()
     rows = rows.to(torch.int32).contiguous()
-    launch_socks_match_replies(stream_bytes, offsets, rows, row_sock, nrows, pending, hdrs, tcall, reply_of)
-    return hdrs, tcall[:n], reply_of[:pending.ncalls]
+    return _match_t(stream_bytes, offsets, pending, lambda hdrs, tcall, treply: launch_socks_match_replies(
+        stream_bytes, offsets, rows, row_sock, nrows, pending, hdrs, tcall, treply))
 
 
 def socks_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, rows: torch.Tensor, pending: SockCalls,
@@ -1351,8 +1361,8 @@ def socks_match_replies(stream_bytes: torch.Tensor, offsets: torch.Tensor, rows:
     None when a row is its socket.  A reply whose xid is pending on another
     socket only is RPCR_UNKNOWN_XID.  Returns (hdrs, call, reply_of) in the
     caller's positions."""
-    hdrs, tcall, reply_of = _socks_match_t(stream_bytes, offsets, rows, pending, ids)
-    return hdrs, pending.to_caller(tcall), reply_of[pending.inv] if pending.ncalls else reply_of
+    hdrs, tcall, treply = _socks_match_t(stream_bytes, offsets, rows, pending, ids)
+    return hdrs, pending.to_caller(tcall), pending.calls_to_caller(treply)
 
 
 def closed_socks(received: Received, ids, nsocks: int, also: torch.Tensor | None = None) -> torch.Tensor:
@@ -1390,17 +1400,7 @@ def socks_settle(received, pending: SockCalls, plans: dict[int, Plan | None], cl
         stream_bytes, offsets, rows = received
     dev, nc = pending.device, pending.ncalls
     hdrs, tcall, treply = _socks_match_t(stream_bytes, offsets, rows, pending, ids)
-    _verify_results_t(stream_bytes, hdrs, tcall, pending, plans, stack_limit)
-    results = {}
-    for res in sorted(plans):
-        data, offs, index = _gather_results_t(stream_bytes, hdrs, tcall, pending, res)
-        if plans[res] is None:
-            results[res] = (index, None, None)
-        elif index.numel() == 0:
-            results[res] = (index, torch.empty(0, dtype=torch.uint8, device=dev), None)
-        else:
-            native, heap = Marshaler(plans[res], dev).decode(data, index.numel(), offs, stack_limit)
-            results[res] = (index, native, heap)
+    results = _decode_matched(stream_bytes, hdrs, tcall, pending, plans, stack_limit)
     closed = closed.to(device=dev, dtype=torch.int32).contiguous()
     count = torch.empty(1, dtype=torch.int64, device=dev)
     stats = torch.empty(max(nc, 1), dtype=torch.int64, device=dev)[:nc]
@@ -1410,18 +1410,9 @@ def socks_settle(received, pending: SockCalls, plans: dict[int, Plan | None], cl
     ws = torch.empty(max(A.lib().xdrg_rpc_socks_pending_retire_workspace_size(nc), 16), dtype=torch.uint8, device=dev)
     launch_socks_call_stats(hdrs, treply, pending, closed, stats)
     launch_socks_pending_retire(pending, treply, closed, kept, kept_sock, kept_pos, count, ws)
-    if nc == 0:
-        e = torch.empty(0, dtype=torch.int64, device=dev)
-        return stats, results, SockCalls.from_device(kept, kept_sock, e, pending.last), e.clone()
-    pos = kept_pos[pending.inv]  # a survivor's new table position, by old caller position
-    alive = pos >= 0
-    rank = torch.cumsum(alive, 0) - 1
-    k = int(count.item())
-    slot = torch.empty(k + 1, dtype=torch.int64, device=dev)
-    slot.scatter_(0, torch.where(alive, rank, k), torch.arange(nc, dtype=torch.int64, device=dev))
-    old_of_new = slot[:k]
-    pending2 = SockCalls.from_device(kept[:k], kept_sock[:k], pos[old_of_new], pending.last)
-    return stats[pending.inv], results, pending2, old_of_new
+    k, inv2, old_of_new = pending._survivors(kept_pos, count)
+    pending2 = SockCalls.from_device(kept[:k], kept_sock[:k], inv2, pending.last)
+    return pending.calls_to_caller(stats), results, pending2, old_of_new
 
 
 def socks_call_batch_any_order(pending: SockCalls, socks, sources: list, capacity: int | None = None):
@@ -1438,7 +1429,7 @@ def socks_call_batch_any_order(pending: SockCalls, socks, sources: list, capacit
     space over many connections needs none of this: call_batch() in caller
     order, then send_batch() with the stream, its offsets and conn = socks.)"""
     import dataclasses
-    srcs = [r if isinstance(r, ArgSource) else arg_source(*r) for r in sources]
+    srcs = _as_arg_sources(sources)
     dev = pending.device
     n = len(socks) if not isinstance(socks, torch.Tensor) else socks.numel()
     call_sock = _sock_tensor(socks, n, dev)
@@ -1569,7 +1560,6 @@ def send_batch(sources: list, nconns: int, closed=None, capacity: int | None = N
         raise ValueError(f"at most {A.RPC_MAX_SEND_SRCS} message streams per call")
     dev = srcs[0].stream.device if srcs else torch.device("cuda")
     entries = sum(r.cap for r in srcs)
-    L = A.lib()
     cap = sum(r.stream.numel() for r in srcs) if capacity is None else capacity
     if closed is not None:
         closed = _sock_tensor(closed, nconns, dev)
@@ -1581,14 +1571,10 @@ def send_batch(sources: list, nconns: int, closed=None, capacity: int | None = N
     pos = torch.empty(max(entries, 1), dtype=torch.int64, device=dev)[:entries]
     queues = torch.empty(max(4 * nconns, 4), dtype=torch.int64, device=dev)[:4 * nconns]
     counts = torch.empty(4, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.xdrg_rpc_send_batch_workspace_size(entries, nconns), 16), dtype=torch.uint8, device=dev)
-    st = Status(dev)
-    s = _stream()
-    st.init(s)
-    launch_send_batch(srcs, nconns, closed, out, offs, cnt, conn_of, origin, pos, queues, counts, st, ws, s)
-    e = st.read(s)
-    if e.code:
-        raise XdrRuntimeError(L.xdrg_error_message(e.code).decode(), int(e.record), None, int(e.code))
+    ws = torch.empty(max(A.lib().xdrg_rpc_send_batch_workspace_size(entries, nconns), 16), dtype=torch.uint8,
+                     device=dev)
+    e = _run_status(dev, lambda st, s: launch_send_batch(srcs, nconns, closed, out, offs, cnt, conn_of, origin, pos,
+                                                         queues, counts, st, ws, s))
     n = int(cnt.item())
     return Queued(out[:int(e.total_bytes)], offs[:n + 1], n, conn_of[:n], origin[:n], pos, queues,
                   tuple(int(v) for v in counts.tolist()))
