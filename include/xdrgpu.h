@@ -89,6 +89,7 @@ extern "C" {
                                    xdrg_rpc_call_batch_workspace_size, xdrg_rpc_pending_add;
                                    (additive, still 10) xdrg_rpc_call_stats, xdrg_rpc_pending_retire,
                                    xdrg_rpc_pending_retire_workspace_size;
+                                   (additive, still 10) xdrg_plan_set_compare_classes, xdrg_compare;
                                9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
 
 /* ---------------------------------------------------------------------- */
@@ -1665,6 +1666,68 @@ int xdrg_serial_sizes(const xdrg_plan *plan, const void *d_native, uint64_t n,
                       const void *d_heap, uint64_t heap_len, uint32_t *d_sizes,
                       uint32_t stack_limit, void *d_workspace, size_t workspace_bytes,
                       xdrg_status *d_status, void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* Comparison: operator== and operator<=> of record batches                */
+/* ---------------------------------------------------------------------- */
+/*
+ * xdrg_compare <- xdr::operator== / operator<=> of xdrpp/types.h:946-1062
+ * (XDRPP_STRONG_ORDER = 0) and pointer's at :647-657, for n record pairs:
+ * structs field by field in declaration order, the first field that is not
+ * equivalent deciding (types.h:1047-1056); unions by discriminant, then by
+ * the active arm (:1030-1044; equal discriminants that select a void arm or
+ * no arm compare equivalent); an absent pointer less than a present one
+ * (:651-657); xvector / xarray as std::vector / std::array (lexicographic,
+ * then the shorter is less); opaque and string bytes as unsigned chars, then
+ * by length; integers by value with their signedness, enums as int32, bools
+ * false < true (any nonzero native byte is true), float and double as IEEE
+ * values (-0.0 equivalent to +0.0, a NaN unordered against everything).
+ * Native padding never influences a result.
+ *
+ * The plan ops do not say whether a word is signed, unsigned or IEEE, so a
+ * plan carries its value classes in a side table beside the ops (the ops
+ * themselves, and everything computed from them, stay as they are):
+ * xdrg_plan_set_compare_classes takes one byte per op -- meaningful on U32,
+ * U64 and UNION ops (the discriminant's class; XDRG_CLASS_BOOL marks a bool
+ * discriminant); an ENUM op is always signed.  XDRG_EINVAL for a wrong nops
+ * or a value out of range.  Host-only; set before the plan's first
+ * xdrg_compare and before the plan is shared between threads.
+ */
+enum xdrg_compare_class {
+  XDRG_CLASS_UNSIGNED = 0,
+  XDRG_CLASS_SIGNED = 1,
+  XDRG_CLASS_IEEE = 2,
+  XDRG_CLASS_BOOL = 3 /* UNION ops only */
+};
+int xdrg_plan_set_compare_classes(xdrg_plan *plan, const uint8_t *classes, uint32_t nops);
+
+enum xdrg_cmp {
+  XDRG_CMP_LESS = -1,
+  XDRG_CMP_EQUAL = 0,     /* a == b holds exactly when the result is this */
+  XDRG_CMP_GREATER = 1,
+  XDRG_CMP_UNORDERED = 2, /* std::partial_ordering::unordered */
+  XDRG_CMP_DEEP = 3,      /* the pair is equal down to a container that would need more than
+                             XDRG_SUB_FRAMES open element frames: not compared */
+  XDRG_CMP_BADREF = 4     /* a bytes or element reference of a or b (with a nonzero length or
+                             count) points outside its heap; nothing is read through it */
+};
+/*
+ * d_result[i] = a[i] <=> b[i] (int8, enum xdrg_cmp).  d_a and d_b are native
+ * record batches of the plan's stride, each with its own heap (the staging
+ * heap, or the heap a decode returned; NULL/0 for plans without references).
+ * Host checks first, then kernels only (no memset, no sync, no allocation
+ * after the plan's first compare on the device, which uploads its tables):
+ * capturable.  n = 0 launches nothing.  XDRG_EINVAL: null arguments;
+ * XDRG_EALIGN: a native base or heap xdrg_encode would refuse (fixed plans:
+ * 4-byte aligned records; var plans: 8-byte aligned records, 4-byte aligned
+ * heaps); XDRG_EUNSUPPORTED: the plan has U32, U64 or UNION ops and no
+ * classes.  Fixed plans whose native stride is a multiple of 16 (and whose
+ * batches are 16-byte aligned) are compared chunk by chunk, a lane per
+ * 16-byte chunk position; everything else by one lane walking the pair.
+ */
+int xdrg_compare(const xdrg_plan *plan, const void *d_a, const void *d_a_heap, uint64_t a_heap_len,
+                 const void *d_b, const void *d_b_heap, uint64_t b_heap_len, uint64_t n,
+                 int8_t *d_result, void *stream);
 
 /* Bulk big-endian swaps (endian.h swap32/swap64) over device arrays. */
 int xdrg_swap32(const uint32_t *d_in, uint32_t *d_out, uint64_t n, void *stream);

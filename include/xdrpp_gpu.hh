@@ -217,6 +217,7 @@ struct discriminant_of<U, std::void_t<typename xdr_traits<U>::discriminant_type>
 // depths relative to the level the type is placed at.
 struct subplan {
   std::vector<xdrg_op> ops;
+  std::vector<std::uint8_t> cls;  // parallel to ops: value classes for xdrg_compare (enum xdrg_compare_class)
   std::vector<std::uint32_t> table;
   std::vector<std::pair<std::uint32_t, std::string>> msgs;  // op -> bad-discriminant what()
   std::uint32_t size = 0, align = 1;
@@ -225,7 +226,7 @@ struct subplan {
   bool validates = false;  // some struct/union in the type has a validate() hook
 
   bool same_ops(const subplan &o) const {
-    if (ops.size() != o.ops.size() || table != o.table) return false;
+    if (ops.size() != o.ops.size() || table != o.table || cls != o.cls) return false;
     for (std::size_t i = 0; i < ops.size(); ++i)
       if (std::memcmp(&ops[i], &o.ops[i], sizeof(xdrg_op)) != 0) return false;
     return true;
@@ -265,6 +266,7 @@ inline void append(subplan &dst, const subplan &src, std::uint32_t base, std::ui
     }
     dst.ops.push_back(o);
   }
+  dst.cls.insert(dst.cls.end(), src.cls.begin(), src.cls.end());
   for (const auto &m : src.msgs) dst.msgs.emplace_back(m.first + pc0, m.second);
 }
 
@@ -454,6 +456,12 @@ template <typename U> subplan record_union() {
     a1 = static_cast<std::uint32_t>(s.size());
   }
   sp.ops.push_back(mkop(XDRG_OP_UNION, 0, 1, a0, a1, flags));
+  {  // the discriminant compares as a value of its declared type (types.h:1030-1044)
+    using D = plain<typename discriminant_of<U>::type>;  // (_xdr_discriminant() itself returns the case type)
+    sp.cls.push_back(std::is_same_v<D, bool>                      ? XDRG_CLASS_BOOL
+                     : std::is_enum_v<D> || std::is_signed_v<D> ? XDRG_CLASS_SIGNED
+                                                                 : XDRG_CLASS_UNSIGNED);
+  }
   if (!message.empty() && !has_default) sp.msgs.emplace_back(0, message);
 
   // arms, each once; identical arms share code
@@ -468,6 +476,7 @@ template <typename U> subplan record_union() {
     append(sp, a.sp, arms_off, 1);
     jumps.push_back(static_cast<std::uint32_t>(sp.ops.size()));
     sp.ops.push_back(mkop(XDRG_OP_JUMP, 0, 1));
+    sp.cls.push_back(0);
     placed.emplace_back(&a.sp, pc);
     return pc;
   };
@@ -495,10 +504,12 @@ template <typename T> subplan record_type() {
   subplan sp;
   if constexpr (std::is_same_v<T, bool>) {
     sp.ops.push_back(mkop(XDRG_OP_BOOL, 0, 0));
+    sp.cls.push_back(0);
     sp.size = sp.align = 1;
   } else if constexpr (bytes_kind<T>::kind != 0) {
     constexpr int k = bytes_kind<T>::kind;
     sp.ops.push_back(mkop(k, 0, 0, bytes_kind<T>::n));
+    sp.cls.push_back(0);
     if constexpr (k == XDRG_OP_OPAQUE) {
       sp.size = bytes_kind<T>::n;
       sp.align = 1;
@@ -520,10 +531,14 @@ template <typename T> subplan record_type() {
     } else {
       sp.ops.push_back(mkop(XDRG_OP_ENUM, 0, 0));
     }
+    sp.cls.push_back(0);  // (an ENUM op is always signed)
     sp.size = sp.align = 4;
   } else if constexpr (TR::is_numeric) {
     using UT = typename TR::uint_type;
     sp.ops.push_back(mkop(sizeof(UT) == 8 ? XDRG_OP_U64 : XDRG_OP_U32, 0, 0));
+    sp.cls.push_back(std::is_floating_point_v<T> ? XDRG_CLASS_IEEE
+                     : std::is_signed_v<T>       ? XDRG_CLASS_SIGNED
+                                                 : XDRG_CLASS_UNSIGNED);
     sp.size = sizeof(T);
     sp.align = alignof(T);
   } else if constexpr (vector_info<T>::value) {
@@ -539,12 +554,14 @@ template <typename T> subplan record_type() {
       xdrg_op v = mkop(XDRG_OP_VECTOR, 0, 1, vector_info<T>::max, align_up(e.size, e.align), fl);
       v.arg2 = static_cast<std::uint32_t>(e.ops.size());
       sp.ops.push_back(v);
+      sp.cls.push_back(0);
       append(sp, e, 0, 1);  // elements inside the container level
       sp.validates = e.validates;
     } else {  // the element's subroutine; stride and body pc set by batch_plan
       xdrg_op v = mkop(XDRG_OP_VECTOR, 0, 1, vector_info<T>::max, 0, fl | XDRG_F_SUB);
       v.arg4 = sub_key<E>();
       sp.ops.push_back(v);
+      sp.cls.push_back(0);
     }
   } else if constexpr (xarray_info<T>::value) {
     using E = typename xarray_info<T>::elem;
@@ -823,6 +840,8 @@ template <typename T> class batch_plan {
   xdrg_plan *handle() const { return h_.get(); }
   const std::vector<xdrg_op> &ops() const { return ops_; }
   const std::vector<std::uint32_t> &table() const { return table_; }
+  //! One value class per op for xdrg_compare (empty: a plan emitted by xdrc -plan).
+  const std::vector<std::uint8_t> &compare_classes() const { return cls_; }
   std::uint32_t stride() const { return stride_; }
   //! Records are passed to the device as-is (staged layout == C++ layout).
   bool identity() const { return identity_; }
@@ -878,6 +897,9 @@ template <typename T> class batch_plan {
                                       static_cast<std::uint32_t>(table_.size()), stride_, &h),
                      "xdrg_plan_create");
     h_.reset(h);
+    if (cls_.size() == ops_.size())  // what xdrg_compare orders the words by
+      detail::abicheck(xdrg_plan_set_compare_classes(h, cls_.data(), static_cast<std::uint32_t>(cls_.size())),
+                       "xdrg_plan_set_compare_classes");
     if (kernels && *kernels) {
       const char *dir = std::getenv("XDRG_PLAN_KERNEL_DIR");
 #ifdef XDRG_EMITTED_KERNEL_DIR
@@ -921,6 +943,7 @@ template <typename T> class batch_plan {
     detail::subplan top;
     detail::append(top, sp, 0, 0);
     top.ops.push_back(detail::mkop(XDRG_OP_END, 0, 0));
+    top.cls.push_back(0);
     // bodies in order of first reference, breadth first from the record
     // (the order xdrpp_amd/xdr_types.py emits them in)
     const std::size_t nk = subs.bodies.size();
@@ -940,6 +963,7 @@ template <typename T> class batch_plan {
       entry[k] = static_cast<std::uint32_t>(top.ops.size());
       detail::append(top, subs.bodies[k], 0, 0);
       top.ops.push_back(detail::mkop(XDRG_OP_END, 0, 0));
+      top.cls.push_back(0);
       validates = validates || subs.bodies[k].validates;
       refs(subs.bodies[k]);
     }
@@ -950,6 +974,7 @@ template <typename T> class batch_plan {
         o.arg4 = entry[o.arg4];
       }
     ops_ = std::move(top.ops);
+    cls_ = std::move(top.cls);
     table_ = std::move(top.table);
     msgs_ = std::move(top.msgs);
     stride_ = detail::align_up(std::max<std::uint32_t>(sp.size, 1), std::max<std::uint32_t>(sp.align, 4));
@@ -962,6 +987,7 @@ template <typename T> class batch_plan {
   template <typename U> friend struct recorded_plan;
   std::unique_ptr<xdrg_plan, deleter> h_;
   std::vector<xdrg_op> ops_;
+  std::vector<std::uint8_t> cls_;  // recorded plans: the value classes (plans emitted by xdrc -plan carry none)
   std::vector<std::uint32_t> table_;
   std::vector<std::pair<std::uint32_t, std::string>> msgs_;
   std::uint32_t stride_ = 0, fixed_size_ = 0;
@@ -975,6 +1001,7 @@ template <typename T> const batch_plan<T> &plan_for() { return batch_plan<T>::ge
 //! one (tests compare the two op for op).
 template <typename T> struct recorded_plan {
   std::vector<xdrg_op> ops;
+  std::vector<std::uint8_t> compare_classes;
   std::vector<std::uint32_t> table;
   std::vector<std::pair<std::uint32_t, std::string>> msgs;
   std::uint32_t stride = 0;
@@ -982,6 +1009,7 @@ template <typename T> struct recorded_plan {
   recorded_plan() {
     const batch_plan<T> r{typename batch_plan<T>::record_only{}};
     ops = r.ops_;
+    compare_classes = r.cls_;
     table = r.table_;
     msgs = r.msgs_;
     stride = r.stride_;
@@ -990,6 +1018,22 @@ template <typename T> struct recorded_plan {
     validates = r.validates_;
   }
 };
+
+// -------------------------------------------------------------- comparison
+//! d_result[i] = a[i] <=> b[i] as enum xdrg_cmp (operator<=> and operator==
+//! of xdrpp/types.h:946-1062: a[i] == b[i] exactly when the result is
+//! XDRG_CMP_EQUAL) for n record pairs already on the device -- staged
+//! batches, or what a decode wrote -- each side with its own heap.  Kernels
+//! only on `s`; nothing is waited for (xdrg_compare).  Plans emitted by
+//! xdrc -plan carry no value classes: XDRG_EUNSUPPORTED for those.
+template <typename T>
+void compare_batch(const void *d_a, const void *d_a_heap, std::uint64_t a_heap_len, const void *d_b,
+                   const void *d_b_heap, std::uint64_t b_heap_len, std::uint64_t n, std::int8_t *d_result,
+                   hipStream_t s = nullptr) {
+  detail::abicheck(xdrg_compare(plan_for<T>().handle(), d_a, d_a_heap, a_heap_len, d_b, d_b_heap, b_heap_len, n,
+                                d_result, s),
+                   "xdrg_compare");
+}
 
 // ---------------------------------------------------------------- staging
 //! Host staging of a batch: records in the staged layout + payload heap.

@@ -26,6 +26,11 @@ MAX_FRAMES = 1 << 19  # XDRG_MAX_FRAMES
 
 PATH_FIXED_REG, PATH_FIXED_LDS, PATH_VAR = 1, 2, 3
 
+# xdrg_plan_set_compare_classes: one byte per op (U32 / U64 / UNION ops; BOOL marks a bool discriminant)
+CMP_CLASS_UNSIGNED, CMP_CLASS_SIGNED, CMP_CLASS_IEEE, CMP_CLASS_BOOL = range(4)
+# xdrg_compare: the int8 result of a pair
+CMP_LESS, CMP_EQUAL, CMP_GREATER, CMP_UNORDERED, CMP_DEEP, CMP_BADREF = -1, 0, 1, 2, 3, 4
+
 # enum xdrg_plan_option (xdrg_plan_set_option)
 PLAN_OPTIONS = {"var_encode_kernel": 1, "var_decode_kernel": 2, "fixed_path": 3, "image_bytes": 4,
                 "window_bytes": 5, "enc_unroll": 6, "dec_readahead": 7, "size_linear": 8,
@@ -150,6 +155,7 @@ EXPORTED = (
     "xdrg_rpc_socks_next_xids", "xdrg_rpc_socks_pending_add", "xdrg_rpc_socks_match_replies",
     "xdrg_rpc_socks_call_stats", "xdrg_rpc_socks_pending_retire", "xdrg_rpc_socks_pending_retire_workspace_size",
     "xdrg_rpc_send_batch", "xdrg_rpc_send_batch_workspace_size",
+    "xdrg_plan_set_compare_classes", "xdrg_compare",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -395,6 +401,10 @@ def lib() -> C.CDLL:
     L.xdrg_error_exception.argtypes = [C.c_int]
     L.xdrg_error_exception.restype = C.c_int
     L.xdrg_last_hip_error.restype = C.c_char_p
+    L.xdrg_plan_set_compare_classes.argtypes = [vp, vp, u32]
+    L.xdrg_plan_set_compare_classes.restype = C.c_int
+    L.xdrg_compare.argtypes = [vp, vp, vp, u64, vp, vp, u64, u64, vp, vp]
+    L.xdrg_compare.restype = C.c_int
     if L.xdrg_abi_version() != ABI_VERSION:
         raise ImportError("libxdrgpu.so ABI version mismatch")
     _lib = L

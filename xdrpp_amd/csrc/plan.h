@@ -80,6 +80,21 @@ struct fixed_prog {
   bool has_bool = false;
 };
 
+// xdrg_compare's chunk kernel (compare_kernels.h): what one 4-byte native
+// word of a fixed record is to operator<=>.  A 64-bit field is compared at
+// its low word (the high word is CW_PAD).  CW_BYTES: the bytes of `bytes`
+// compare as unsigned chars in memory order (opaque), those of `bools` as
+// bools (nonzero = true); every other byte is padding.
+enum cmp_word_kind : uint32_t {
+  CW_PAD = 0, CW_U32 = 1, CW_S32 = 2, CW_F32 = 3, CW_BYTES = 4, CW_U64 = 5, CW_S64 = 6, CW_F64 = 7
+};
+struct cmp_word {
+  uint32_t kind;
+  uint32_t bytes;
+  uint32_t bools;
+  uint32_t rsv;
+};
+
 // A plan's tables in one device's memory.
 struct dev_tables {
   void *d_mem = nullptr;
@@ -164,6 +179,17 @@ struct xdrg_plan {
   // plan-specialized kernels (var plans): generated source, code object,
   // per-device modules
   xdrg::spec_state spec;
+  // xdrg_compare (compare.hip): the value classes beside the ops
+  // (xdrg_plan_set_compare_classes), what the launcher builds from them --
+  // per op its class and, for a UNION op, the pc behind the union; for
+  // plans the chunk kernel serves, the word program -- and their device
+  // copies, uploaded by the plan's first compare on a device.
+  bool has_cmp = false;
+  bool cmp_fixed = false;               // k_cmp_fixed serves the plan
+  std::vector<uint32_t> cmp_info;       // [nops] class | behind-the-union pc << 8
+  std::vector<xdrg::cmp_word> cmp_prog; // [stride / 4] when cmp_fixed
+  std::atomic<bool> cmp_uploaded[xdrg::kMaxDevices] = {};
+  void *cmp_dev[xdrg::kMaxDevices] = {};  // cmp_info, then cmp_prog (256-byte aligned)
 };
 
 namespace xdrg {

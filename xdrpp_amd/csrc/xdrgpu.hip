@@ -2940,9 +2940,10 @@ void xdrg_plan_destroy(xdrg_plan *p) {
   int cur = 0;
   const bool restore = hipGetDevice(&cur) == hipSuccess;
   for (int d = 0; d < kMaxDevices; ++d)
-    if (p->dev[d].d_mem) {
+    if (p->dev[d].d_mem || p->cmp_dev[d]) {
       (void)hipSetDevice(d);
-      (void)hipFree(p->dev[d].d_mem);
+      if (p->dev[d].d_mem) (void)hipFree(p->dev[d].d_mem);
+      if (p->cmp_dev[d]) (void)hipFree(p->cmp_dev[d]);  // xdrg_compare's tables (compare.hip)
     }
   if (restore) (void)hipSetDevice(cur);
   delete p;

@@ -78,6 +78,10 @@ class Plan:
             None if table is None else table.ctypes.data_as(C.POINTER(C.c_uint32)),
             0 if table is None else table.size, self.cp.stride, C.byref(h)), "xdrg_plan_create")
         self.handle = h
+        cls = self.cp.cmp_classes
+        if cls is not None:  # the value classes xdrg_compare orders the words by
+            A.check(L.xdrg_plan_set_compare_classes(h, cls.ctypes.data_as(C.c_void_p), len(cls)),
+                    "xdrg_plan_set_compare_classes")
         for k, v in (options or {}).items():
             A.check(L.xdrg_plan_set_option(h, A.PLAN_OPTIONS[k], int(v)), f"xdrg_plan_set_option({k})")
         info = A.XdrgPlanInfo()
@@ -235,6 +239,25 @@ class Marshaler:
             _ptr(native_out), _ptr(heap_out), 0 if heap_out is None else heap_out.numel(),
             stack_limit, dw, dn, self.status.ptr, _stream() if stream is None else stream),
             "xdrg_decode_msgs")
+
+    def launch_compare(self, a, b, n, out, heap_a=None, heap_b=None, stream=None):
+        """xdrg_compare: out[i] (int8) = a[i] <=> b[i] as _abi.CMP_*; kernels
+        only, nothing is waited for."""
+        A.check(A.lib().xdrg_compare(
+            self.plan.handle, _ptr(a), _ptr(heap_a), 0 if heap_a is None else heap_a.numel(),
+            _ptr(b), _ptr(heap_b), 0 if heap_b is None else heap_b.numel(), n, _ptr(out),
+            _stream() if stream is None else stream), "xdrg_compare")
+
+    def compare(self, a, b, n, heap_a=None, heap_b=None) -> torch.Tensor:
+        """operator<=> of n record pairs (xdrpp/types.h:946-1062): int8[n] of
+        _abi.CMP_LESS / EQUAL / GREATER / UNORDERED (/ DEEP / BADREF)."""
+        out = torch.empty(max(n, 1), dtype=torch.int8, device=self.device)
+        self.launch_compare(a, b, n, out, heap_a, heap_b)
+        return out[:n]
+
+    def equal(self, a, b, n, heap_a=None, heap_b=None) -> torch.Tensor:
+        """operator== of n record pairs: bool[n]."""
+        return self.compare(a, b, n, heap_a, heap_b) == A.CMP_EQUAL
 
     def check(self, stream=None) -> A.XdrgError:
         e = self.status.read(_stream() if stream is None else stream)

@@ -62,6 +62,7 @@ class _Ctx:
 
     def __init__(self) -> None:
         self.ops: list[list[int]] = []  # [kind, flags, depth, noff, a0..a4, name]
+        self.classes: list[int] = []    # per op: its value class for xdrg_compare (CMP_CLASS_*)
         self.table: list[int] = []
         self.names: list[str] = []      # name id -> dotted field path
         self.messages: dict[int, str] = {}  # op index -> bad-discriminant what()
@@ -93,8 +94,9 @@ class _Ctx:
         self.names.append(path)
         return len(self.names) - 1
 
-    def emit(self, kind, noff, depth, path, flags=0, a0=0, a1=0, a2=0, a3=0, a4=0) -> int:
+    def emit(self, kind, noff, depth, path, flags=0, a0=0, a1=0, a2=0, a3=0, a4=0, cls=0) -> int:
         self.ops.append([kind, flags, depth, noff, a0, a1, a2, a3, a4, self.name(path)])
+        self.classes.append(cls)  # a side table: the ops themselves do not change
         return len(self.ops) - 1
 
     def add_table(self, values) -> int:
@@ -114,22 +116,23 @@ class XdrType:
 
 
 class _Scalar(XdrType):
-    def __init__(self, name, kind, size, wire):
+    def __init__(self, name, kind, size, wire, cls=A.CMP_CLASS_UNSIGNED):
         self.name, self.kind, self.size, self.align, self.fixed_wire = name, kind, size, size, wire
+        self.cls = cls  # how operator<=> orders the word (xdrg_plan_set_compare_classes)
 
     def emit(self, ctx, noff, depth, path):
-        ctx.emit(self.kind, noff, depth, path)
+        ctx.emit(self.kind, noff, depth, path, cls=self.cls)
 
     def __repr__(self):
         return self.name
 
 
-Int = _Scalar("int", A.OP_U32, 4, 4)
+Int = _Scalar("int", A.OP_U32, 4, 4, A.CMP_CLASS_SIGNED)
 UInt = _Scalar("unsigned", A.OP_U32, 4, 4)
-Float = _Scalar("float", A.OP_U32, 4, 4)
-Hyper = _Scalar("hyper", A.OP_U64, 8, 8)
+Float = _Scalar("float", A.OP_U32, 4, 4, A.CMP_CLASS_IEEE)
+Hyper = _Scalar("hyper", A.OP_U64, 8, 8, A.CMP_CLASS_SIGNED)
 UHyper = _Scalar("unsigned hyper", A.OP_U64, 8, 8)
-Double = _Scalar("double", A.OP_U64, 8, 8)
+Double = _Scalar("double", A.OP_U64, 8, 8, A.CMP_CLASS_IEEE)
 Bool = _Scalar("bool", A.OP_BOOL, 1, 4)
 
 
@@ -345,8 +348,10 @@ class Union(XdrType):
         if isinstance(self.tag_type, Enum) and self.tag_type.validate:
             vals = sorted(set(self.tag_type.tags.values()))
             flags, a0, a1 = A.F_VALIDATE, ctx.add_table(vals), len(vals)
+        # the discriminant compares as a value of its declared type (types.h:1030-1044)
+        cls = A.CMP_CLASS_BOOL if self.tag_type is Bool else getattr(self.tag_type, "cls", A.CMP_CLASS_SIGNED)
         upc = ctx.emit(A.OP_UNION, noff, d, f"{path}.{self.tag_name}" if path else self.tag_name,
-                       flags, a0, a1)
+                       flags, a0, a1, cls=cls)
         ctx.messages[upc] = self.message()
         targets, jumps = [], []  # (case, pc or None for void)
         arm_base = noff + self.arms_off
@@ -388,9 +393,11 @@ class CompiledPlan:
     """Host-side result of compiling a type: the op array and table exactly as
     passed to xdrg_plan_create, plus names for error messages."""
 
-    def __init__(self, root: XdrType, ops: np.ndarray, table: np.ndarray, names, messages):
+    def __init__(self, root: XdrType, ops: np.ndarray, table: np.ndarray, names, messages, cmp_classes=None):
         self.root = root
         self.ops = ops
+        # uint8 per op for xdrg_plan_set_compare_classes (None: a plan built without them)
+        self.cmp_classes = cmp_classes
         self.table = table
         self.names = names
         self.messages = messages
@@ -421,4 +428,4 @@ def compile_plan(root: XdrType) -> CompiledPlan:
     for i, o in enumerate(ctx.ops):
         ops[i] = tuple(o)
     table = np.array(ctx.table, dtype=np.uint32)
-    return CompiledPlan(root, ops, table, ctx.names, ctx.messages)
+    return CompiledPlan(root, ops, table, ctx.names, ctx.messages, np.array(ctx.classes, dtype=np.uint8))
