@@ -90,6 +90,7 @@ extern "C" {
                                    (additive, still 10) xdrg_rpc_call_stats, xdrg_rpc_pending_retire,
                                    xdrg_rpc_pending_retire_workspace_size;
                                    (additive, still 10) xdrg_plan_set_compare_classes, xdrg_compare;
+                                   (additive, still 10) xdrg_sort_workspace_size, xdrg_sort;
                                9: xdrg_verify, xdrg_rpc_verify_args, xdrg_rpc_gather_args */
 
 /* ---------------------------------------------------------------------- */
@@ -1728,6 +1729,51 @@ enum xdrg_cmp {
 int xdrg_compare(const xdrg_plan *plan, const void *d_a, const void *d_a_heap, uint64_t a_heap_len,
                  const void *d_b, const void *d_b_heap, uint64_t b_heap_len, uint64_t n,
                  int8_t *d_result, void *stream);
+
+/*
+ * xdrg_sort <- std::stable_sort and std::unique of a batch by xdr::operator<
+ * (xdrpp/types.h:946-1062, XDRPP_STRONG_ORDER = 0), as a permutation: no
+ * record moves.  d_recs is one native batch of the plan's stride with its
+ * heap, as one side of xdrg_compare.
+ *
+ * Record i is sortable when rec[i] <=> rec[i] is XDRG_CMP_EQUAL under
+ * xdrg_compare's rules: not a record that holds a NaN in a field its own walk
+ * reaches, nor one with a reference outside the heap (BADREF), nor one nested
+ * past the register frames (DEEP); xdrg_compare(recs, recs) tells which.
+ * With m the number of sortable records:
+ *
+ *   d_perm[0..m)   the sortable records' indices in the order std::stable_sort
+ *                  gives them: ascending, equivalent records in input order --
+ *                  the one ascending order of the keys (record, index)
+ *   d_perm[m..n)   the other records' indices, in input order
+ *   d_first[k]     (may be NULL) k < m: 1 if k == 0 or rec[perm[k-1]] <
+ *                  rec[perm[k]], else 0 -- a 1 starts a group of equivalent
+ *                  records (std::unique, the contents of a std::set);
+ *                  k >= m: 1 (such a record equals nothing, itself included)
+ *   d_counts[0]    m
+ *   d_counts[1]    the ones in d_first[0..m): the distinct values (computed
+ *                  with or without d_first)
+ *
+ * Host checks first, before any HIP call: XDRG_EINVAL for a null plan, or
+ * with n > 0 null records, perm, counts or workspace, for a heap length
+ * without a heap, for workspace_bytes below xdrg_sort_workspace_size(plan,
+ * n); XDRG_EALIGN for records or a heap xdrg_compare would refuse, a
+ * workspace that is not 16-byte aligned, a d_perm that is not 4-byte or
+ * d_counts that is not 8-byte aligned; XDRG_EUNSUPPORTED for n > 2^31 (the
+ * size is 0 then) and for a plan with U32, U64 or UNION ops and no classes.
+ * n = 0 launches nothing and writes nothing.
+ *
+ * Then kernels only (no memset, no memcpy, no sync, no allocation after the
+ * plan's first compare or sort on the device, which uploads the class
+ * table): capturable.  The number of launches depends on n alone; m is never
+ * read on the host.  Every store is in bounds whatever the bytes of the
+ * batch.  Every plan sorts by the pair walk, ceil(log2 n) merge passes by
+ * rank, the first eight in one launch.
+ */
+size_t xdrg_sort_workspace_size(const xdrg_plan *plan, uint64_t n);
+int xdrg_sort(const xdrg_plan *plan, const void *d_recs, const void *d_heap, uint64_t heap_len, uint64_t n,
+              uint32_t *d_perm, uint8_t *d_first /* may be NULL */, uint64_t *d_counts /* [2] */,
+              void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Bulk big-endian swaps (endian.h swap32/swap64) over device arrays. */
 int xdrg_swap32(const uint32_t *d_in, uint32_t *d_out, uint64_t n, void *stream);

@@ -1035,6 +1035,25 @@ void compare_batch(const void *d_a, const void *d_a_heap, std::uint64_t a_heap_l
                    "xdrg_compare");
 }
 
+//! Bytes of workspace sort_batch<T> takes for n records.
+template <typename T> std::size_t sort_workspace_size(std::uint64_t n) {
+  return xdrg_sort_workspace_size(plan_for<T>().handle(), n);
+}
+//! std::stable_sort / std::unique of n records already on the device by
+//! operator< of xdrpp/types.h:946-1062, as a permutation: d_perm the
+//! sortable records ascending and the others behind them, d_first (may be
+//! null) the first of each group of equivalent records, d_counts[2] the
+//! sortable and the distinct ones (xdrg_sort).  Kernels only on `s`;
+//! nothing is waited for.
+template <typename T>
+void sort_batch(const void *d_recs, const void *d_heap, std::uint64_t heap_len, std::uint64_t n,
+                std::uint32_t *d_perm, std::uint8_t *d_first, std::uint64_t *d_counts, void *d_workspace,
+                std::size_t workspace_bytes, hipStream_t s = nullptr) {
+  detail::abicheck(xdrg_sort(plan_for<T>().handle(), d_recs, d_heap, heap_len, n, d_perm, d_first, d_counts,
+                             d_workspace, workspace_bytes, s),
+                   "xdrg_sort");
+}
+
 // ---------------------------------------------------------------- staging
 //! Host staging of a batch: records in the staged layout + payload heap.
 //! (A context stages into pinned memory, so that the copies to the device

@@ -156,6 +156,7 @@ EXPORTED = (
     "xdrg_rpc_socks_call_stats", "xdrg_rpc_socks_pending_retire", "xdrg_rpc_socks_pending_retire_workspace_size",
     "xdrg_rpc_send_batch", "xdrg_rpc_send_batch_workspace_size",
     "xdrg_plan_set_compare_classes", "xdrg_compare",
+    "xdrg_sort_workspace_size", "xdrg_sort",
 )
 
 # RPC header batches (include/xdrgpu.h "RPC header batches")
@@ -405,6 +406,10 @@ def lib() -> C.CDLL:
     L.xdrg_plan_set_compare_classes.restype = C.c_int
     L.xdrg_compare.argtypes = [vp, vp, vp, u64, vp, vp, u64, u64, vp, vp]
     L.xdrg_compare.restype = C.c_int
+    L.xdrg_sort_workspace_size.argtypes = [vp, u64]
+    L.xdrg_sort_workspace_size.restype = C.c_size_t
+    L.xdrg_sort.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, vp, C.c_size_t, vp]
+    L.xdrg_sort.restype = C.c_int
     if L.xdrg_abi_version() != ABI_VERSION:
         raise ImportError("libxdrgpu.so ABI version mismatch")
     _lib = L

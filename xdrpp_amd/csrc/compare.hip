@@ -13,8 +13,8 @@
 
 #include <algorithm>
 
+#include "compare_host.h"
 #include "compare_kernels.h"
-#include "host_common.h"
 
 using namespace xdrg;
 using namespace xdrg::dev;
@@ -85,10 +85,28 @@ bool build_word_program(const xdrg_plan &p, const uint8_t *cls, std::vector<cmp_
   return true;
 }
 
-struct cmp_tables {
-  const uint32_t *d_info;
-  const cmp_word *d_prog;
-};
+bool needs_classes(const xdrg_plan &p) {
+  for (const xdrg_op &op : p.ops)
+    if (op.kind == XDRG_OP_U32 || op.kind == XDRG_OP_U64 || op.kind == XDRG_OP_UNION) return true;
+  return false;
+}
+
+void install_classes(xdrg_plan &p, const uint8_t *cls) {
+  p.cmp_info.assign(p.ops.size(), 0u);
+  for (uint32_t i = 0; i < p.ops.size(); ++i)
+    p.cmp_info[i] = cls[i] | (p.ops[i].kind == XDRG_OP_UNION ? union_end(p, i) << 8 : 0u);
+  p.cmp_fixed = build_word_program(p, cls, p.cmp_prog);
+  if (!p.cmp_fixed) p.cmp_prog.clear();
+  p.has_cmp = true;
+}
+
+constexpr uint32_t kCmpMaxBlocks = 1u << 22;  // past it the chunk kernel's waves loop
+
+}  // namespace
+
+namespace xdrg {
+namespace host {
+
 int cmp_upload(const xdrg_plan *cp, cmp_tables *out) {
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
@@ -117,25 +135,20 @@ int cmp_upload(const xdrg_plan *cp, cmp_tables *out) {
   return XDRG_OK;
 }
 
-bool needs_classes(const xdrg_plan &p) {
-  for (const xdrg_op &op : p.ops)
-    if (op.kind == XDRG_OP_U32 || op.kind == XDRG_OP_U64 || op.kind == XDRG_OP_UNION) return true;
-  return false;
+int cmp_classes_ready(const xdrg_plan *plan) {
+  if (plan->has_cmp) return XDRG_OK;
+  if (needs_classes(*plan)) return XDRG_EUNSUPPORTED;
+  // nothing to classify (bools, enums, bytes): every class is 0
+  std::lock_guard<std::mutex> g(const_cast<xdrg_plan *>(plan)->upload_mu);
+  if (!plan->has_cmp) {
+    const std::vector<uint8_t> zero(plan->ops.size(), 0);
+    install_classes(*const_cast<xdrg_plan *>(plan), zero.data());
+  }
+  return XDRG_OK;
 }
 
-void install_classes(xdrg_plan &p, const uint8_t *cls) {
-  p.cmp_info.assign(p.ops.size(), 0u);
-  for (uint32_t i = 0; i < p.ops.size(); ++i)
-    p.cmp_info[i] = cls[i] | (p.ops[i].kind == XDRG_OP_UNION ? union_end(p, i) << 8 : 0u);
-  p.cmp_fixed = build_word_program(p, cls, p.cmp_prog);
-  if (!p.cmp_fixed) p.cmp_prog.clear();
-  p.has_cmp = true;
-}
-
-constexpr uint32_t kCmpMaxBlocks = 1u << 22;  // past it the chunk kernel's waves loop
-constexpr size_t kCmpLdsOps = 48u << 10;      // plans whose ops and classes fit are walked from LDS
-
-}  // namespace
+}  // namespace host
+}  // namespace xdrg
 
 extern "C" {
 
@@ -161,22 +174,15 @@ int xdrg_compare(const xdrg_plan *plan, const void *d_a, const void *d_a_heap, u
   if (misaligned(d_a, var ? 7 : 3) || misaligned(d_b, var ? 7 : 3) || misaligned(d_a_heap, 3) ||
       misaligned(d_b_heap, 3))
     return XDRG_EALIGN;
-  if (!plan->has_cmp) {
-    if (needs_classes(*plan)) return XDRG_EUNSUPPORTED;
-    // nothing to classify (bools, enums, bytes): every class is 0
-    std::lock_guard<std::mutex> g(const_cast<xdrg_plan *>(plan)->upload_mu);
-    if (!plan->has_cmp) {
-      const std::vector<uint8_t> zero(plan->ops.size(), 0);
-      install_classes(*const_cast<xdrg_plan *>(plan), zero.data());
-    }
-  }
+  int rc = cmp_classes_ready(plan);
+  if (rc != XDRG_OK) return rc;
   if (n == 0) return XDRG_OK;
   const uint32_t nops = uint32_t(plan->ops.size());
   const bool chunks = plan->cmp_fixed && !misaligned(d_a, 15) && !misaligned(d_b, 15);
   const uint64_t walk_blocks = (n + 255u) / 256u;
   if (!chunks && walk_blocks > 0x7fffffffull) return XDRG_EUNSUPPORTED;
   const dev_tables *T = nullptr;
-  int rc = plan_tables(plan, &T);
+  rc = plan_tables(plan, &T);
   if (rc != XDRG_OK) return rc;
   cmp_tables C = {};
   rc = cmp_upload(plan, &C);

@@ -218,28 +218,18 @@ struct cmp_stack {
   }
 };
 
-// One lane, one pair.  info[pc] = class | (pc behind the union) << 8.
+// One lane, one pair: the records at ra and rb with their heaps.  ops and
+// info are the plan's, in LDS when LDSOPS (cmp_lds_ops) or in global memory;
+// info[pc] = class | (pc behind the union) << 8.  The walk of (a, b) follows
+// the common path of the walks of (a, a) and (b, b): equal discriminants
+// select the arm both took, a container compares min(count_a, count_b)
+// elements.  xdrg_compare runs it once per pair, xdrg_sort (sort_kernels.h)
+// as its comparator.
 template <bool LDSOPS>
-__global__ __launch_bounds__(256) void k_cmp_walk(const uint8_t *__restrict__ a, const uint8_t *__restrict__ ah,
-                                                  uint64_t ahl, const uint8_t *__restrict__ b,
-                                                  const uint8_t *__restrict__ bh, uint64_t bhl, uint64_t n,
-                                                  uint32_t stride, const xdrg_op *__restrict__ g_ops,
-                                                  const uint32_t *__restrict__ g_info, uint32_t nops,
-                                                  const uint32_t *__restrict__ table, int8_t *__restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t cmp_smem[];
-  const xdrg_op *ops = g_ops;
-  const uint32_t *info = g_info;
-  if constexpr (LDSOPS) {
-    xdrg_op *sops = reinterpret_cast<xdrg_op *>(cmp_smem);
-    uint32_t *sinfo = cmp_smem + 8u * nops;
-    for (uint32_t i = threadIdx.x; i < nops; i += blockDim.x) sinfo[i] = g_info[i];
-    load_ops(sops, g_ops, nops);  // (ends with the barrier)
-    ops = sops;
-    info = sinfo;
-  }
-  const uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const uint8_t *const ra = a + r * stride, *const rb = b + r * stride;
+__device__ __forceinline__ int8_t cmp_walk_pair(const uint8_t *const ra, const uint8_t *const rb,
+                                                const uint8_t *__restrict__ ah, uint64_t ahl,
+                                                const uint8_t *__restrict__ bh, uint64_t bhl, const xdrg_op *ops,
+                                                const uint32_t *info, const uint32_t *__restrict__ table) {
   const uint8_t *ca = ra, *cb = rb;  // the objects the walk is in: the records, or two elements
   cmp_stack S;
   uint32_t fp = 0, pc = 0;
@@ -333,7 +323,35 @@ __global__ __launch_bounds__(256) void k_cmp_walk(const uint8_t *__restrict__ a,
     if (res != R_EQ) { fin = cmp_result(res); break; }
     ++pc;
   }
-  out[r] = fin;
+  return fin;
+}
+
+// The plan's ops and info into the workgroup's dynamic LDS (36 bytes per op),
+// every lane of the workgroup calling; ends with a barrier.
+__device__ __forceinline__ void cmp_lds_ops(const xdrg_op *__restrict__ g_ops, const uint32_t *__restrict__ g_info,
+                                            uint32_t nops, const xdrg_op **ops, const uint32_t **info) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t cmp_smem[];
+  xdrg_op *sops = reinterpret_cast<xdrg_op *>(cmp_smem);
+  uint32_t *sinfo = cmp_smem + 8u * nops;
+  for (uint32_t i = threadIdx.x; i < nops; i += blockDim.x) sinfo[i] = g_info[i];
+  load_ops(sops, g_ops, nops);  // (ends with the barrier)
+  *ops = sops;
+  *info = sinfo;
+}
+
+template <bool LDSOPS>
+__global__ __launch_bounds__(256) void k_cmp_walk(const uint8_t *__restrict__ a, const uint8_t *__restrict__ ah,
+                                                  uint64_t ahl, const uint8_t *__restrict__ b,
+                                                  const uint8_t *__restrict__ bh, uint64_t bhl, uint64_t n,
+                                                  uint32_t stride, const xdrg_op *__restrict__ g_ops,
+                                                  const uint32_t *__restrict__ g_info, uint32_t nops,
+                                                  const uint32_t *__restrict__ table, int8_t *__restrict__ out) {
+  const xdrg_op *ops = g_ops;
+  const uint32_t *info = g_info;
+  if constexpr (LDSOPS) cmp_lds_ops(g_ops, g_info, nops, &ops, &info);
+  const uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  out[r] = cmp_walk_pair<LDSOPS>(a + r * stride, b + r * stride, ah, ahl, bh, bhl, ops, info, table);
 }
 
 }  // namespace dev

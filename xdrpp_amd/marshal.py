@@ -181,6 +181,14 @@ class EncodeResult:
     offsets: torch.Tensor | None  # uint64-as-int64 [n+1] record offsets (var plans)
 
 
+@dataclass
+class Sorted:
+    perm: torch.Tensor   # int32[n]: sortable records ascending (stable), then the others in input order
+    first: torch.Tensor  # uint8[n]: 1 where a group of equivalent records starts
+    sortable: int        # m
+    distinct: int        # the ones in first[:m]
+
+
 class Marshaler:
     """Reusable encode/decode launcher for one plan: owns the status block
     and the var-plan workspace so repeated calls allocate nothing."""
@@ -258,6 +266,44 @@ class Marshaler:
     def equal(self, a, b, n, heap_a=None, heap_b=None) -> torch.Tensor:
         """operator== of n record pairs: bool[n]."""
         return self.compare(a, b, n, heap_a, heap_b) == A.CMP_EQUAL
+
+    def sort_workspace(self, n: int) -> torch.Tensor:
+        """A workspace xdrg_sort takes for n records (uint8, 256-byte aligned)."""
+        need = int(A.lib().xdrg_sort_workspace_size(self.plan.handle, n))
+        return torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+
+    def launch_sort(self, recs, n, perm, first, counts, heap=None, workspace=None, stream=None):
+        """xdrg_sort: perm (int32[n]), first (uint8[n] or None) and counts
+        (int64[2]: sortable, distinct) as include/xdrgpu.h states them;
+        kernels only, nothing is waited for.  Without a workspace
+        (sort_workspace) one is allocated."""
+        ws = self.sort_workspace(n) if workspace is None else workspace
+        A.check(A.lib().xdrg_sort(
+            self.plan.handle, _ptr(recs), _ptr(heap), 0 if heap is None else heap.numel(), n,
+            perm.data_ptr(), None if first is None else first.data_ptr(), counts.data_ptr(),
+            ws.data_ptr(), ws.numel(), _stream() if stream is None else stream), "xdrg_sort")
+
+    def sort(self, recs, n, heap=None) -> "Sorted":
+        """std::stable_sort of n records by operator< (xdrpp/types.h:946-1062)
+        as a permutation, the unsortable records (NaN, bad reference, too
+        deep) behind the sortable ones; first marks the first of each group of
+        equivalent records.  Reads the two counts (one sync)."""
+        if n == 0:
+            return Sorted(torch.empty(0, dtype=torch.int32, device=self.device),
+                          torch.empty(0, dtype=torch.uint8, device=self.device), 0, 0)
+        perm = torch.empty(n, dtype=torch.int32, device=self.device)
+        first = torch.empty(n, dtype=torch.uint8, device=self.device)
+        counts = torch.empty(2, dtype=torch.int64, device=self.device)
+        self.launch_sort(recs, n, perm, first, counts, heap)
+        m, distinct = (int(v) for v in counts.cpu())
+        return Sorted(perm, first, m, distinct)
+
+    def unique(self, recs, n, heap=None) -> torch.Tensor:
+        """One index per distinct sortable value, the values ascending (the
+        earliest record of each group): std::unique after std::stable_sort,
+        the contents of a std::set."""
+        s = self.sort(recs, n, heap)
+        return s.perm[:s.sortable][s.first[:s.sortable] == 1]
 
     def check(self, stream=None) -> A.XdrgError:
         e = self.status.read(_stream() if stream is None else stream)
